@@ -2,7 +2,7 @@
 """Headline benchmark: frames/s of the Accel-18 inference path on 1024x2048
 clips at key-frame interval 5 (BASELINE.json metric, configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = one clip per GPU = 1 key frame + 4 non-key frames through the HIP
@@ -11,13 +11,18 @@ branch, two heads, fused upsample+correction+argmax).  Frames are synthetic,
 weights seeded random (no checkpoints/data offline); the clip is resident in
 HBM before the timed region; outputs (fp32 logits + uint8 labels) stay in HBM;
 with N > 1 every frame's logits are gathered to rank 0 over RCCL, overlapped.
-Prints ONE JSON line on rank 0.  At N = 1 the same line carries `secondary` measurements taken with the same harness
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints that
+line: nothing else.  --full adds everything else the benchmark measures: the conv roofline (`roofline`, --no-roofline
+skips it), the CPU oracle's rate (`cpu_baseline`, --no-cpu-baseline skips it), with N > 1 the steps once more with the
+other gather payload (`gather_rates`), and at N = 1 `secondary` measurements taken with the same harness
 (--secondary none skips them): Accel-101 (the other model BASELINE.json's metric names), Accel-18 at one clip per call
 (the reference's TEST.BATCH_IMAGES: 1), and the PCIe-inclusive rate of the reference's own timing definition
 (demo.py:234-250: host frame in, forward, label map back on the host) through page-locked, double-buffered transfers.
-`vs_baseline` compares like with like: the PCIe-inclusive batch-1 rate against the reference's published K80 number.
+`vs_baseline` compares like with like: the PCIe-inclusive batch-1 rate against the reference's published K80 number
+(--full only; null otherwise).
 """
 import argparse
+import concurrent.futures
 import json
 import os
 import sys
@@ -36,7 +41,7 @@ K80_ACCEL18_FPS = 1.0 / 0.44    # BASELINE.md section 1 (reference README.md:65)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps (>= 1); ms_per_step = their wall time / this number")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--version", default="18")
     ap.add_argument("--size", default="1024x2048")
@@ -54,8 +59,14 @@ def parse():
                          "operand split exactly into three bf16 terms, six products on the bf16 matrix cores, fp32 accumulate "
                          "(fp32-equivalent results, tests/test_bf16x3_gpu.py); f16 = fp16-MFMA convolutions with fp32 storage/"
                          "accumulate (BASELINE config 5: reduced precision, never the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: roofline, cpu_baseline, secondary (N = 1) and "
+                         "gather_rates (N > 1); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32, a fixed "
+                         "seeded sample of the pixels, under 64 MB in all): see OutputDump")
     ap.add_argument("--secondary", default="auto", choices=["auto", "none"],
-                    help="auto: on a single GPU with the headline configuration also measure Accel-101, batch 1 and the "
+                    help="with --full: auto: on a single GPU with the headline configuration also measure Accel-101, batch 1 and the "
                          "PCIe-inclusive loop (reported under `secondary`); none: headline only")
     ap.add_argument("--root-relief", type=int, default=-1,
                     help="N > 1 with --gather scores | logits: rank 0 (which also receives -- and with scores expands -- every other rank's frames) "
@@ -72,9 +83,12 @@ def parse():
                          "not arrive; with this flag alone the job stops after the preflight and rank 0 prints its record")
     ap.add_argument("--watchdog", type=float, default=60.0, help="seconds a phase of a multi-rank job (communicator, preflight, one step) may take")
     ap.add_argument("--rank-logs", default=None, help="directory for the stdout of ranks > 0 (default: gpurun_out/ if it exists, else the temp directory)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def cpu_baseline(version, interval, H=1024, W=2048):
@@ -330,10 +344,14 @@ class Workload(object):
         self.key, _ = self.runner.key_predictor.plan_for(H, W, B)
         self.cur, _ = self.runner.cur_predictor.plan_for(H, W, B)
         self.cur_b, _ = self.runner.cur_predictor.plan_for(H, W, B, slot=1)     # ping-pong partner (the same plan if unpaired)
-        # B clips, distinct per rank and clip: frames[t] = frame t of every clip, (B, 3, H, W) fp32, mean-subtracted
-        clips = [synth.make_clip(H, W, interval, seed=20260929 + rank * 64 + b) for b in range(B)]
-        self.host_frames = [np.concatenate([image.transform(c[t], config.network.PIXEL_MEANS).astype(np.float32) for c in clips], axis=0)
-                            for t in range(interval)]
+        # B clips, distinct per rank and clip: frames[t] = frame t of every clip, (B, 3, H, W) fp32, mean-subtracted.  Each clip is
+        # a pure function of its seed; they are made on a few threads (numpy releases the GIL), the same arrays as one after another
+        def clip(b):
+            return [image.transform(f, config.network.PIXEL_MEANS).astype(np.float32)
+                    for f in synth.make_clip(H, W, interval, seed=20260929 + rank * 64 + b)]
+        with concurrent.futures.ThreadPoolExecutor(max(1, min(B, 8))) as ex:
+            clips = list(ex.map(clip, range(B)))
+        self.host_frames = [np.concatenate([c[t] for c in clips], axis=0) for t in range(interval)]
         self.dev_frames = [torch.from_numpy(f).cuda() for f in self.host_frames]
         self.nbytes = B * 3 * H * W * 4
         self.gather = None
@@ -343,8 +361,9 @@ class Workload(object):
     def scores_gather(self):
         return type(self.gather).__name__ == "ScoreGather"
 
-    def step(self):
-        """one clip per lane: key frame + (interval - 1) non-key frames, inputs and outputs in HBM"""
+    def step(self, capture=None):
+        """one clip per lane: key frame + (interval - 1) non-key frames, inputs and outputs in HBM; capture(t), if given, is
+        called right after frame t's plan is enqueued (OutputDump)"""
         m = self.model
         # the frames are resident in HBM and are COPIED into the model's input buffers every frame, as the reference's executor does
         # with a source array on the device (executor_group._load_general: d_src.copyto(d_targets), unconditionally); the headline
@@ -359,6 +378,8 @@ class Workload(object):
                 put("data_key", self.dev_frames[t - 1].data_ptr(), self.nbytes)
                 plan = self.cur if t % 2 else self.cur_b      # frame 1 reads the key plan's `feat`, frame 2 `feat_b`, ...
             plan.run()
+            if capture is not None:
+                capture(t)
             if self.gather is not None:
                 self.gather.submit(plan) if self.scores_gather else self.gather.submit()
 
@@ -368,7 +389,8 @@ class Workload(object):
         self.model.ctx.sync()
         self.torch.cuda.synchronize()
 
-    def timed(self, steps, warmup, dist=None):
+    def timed(self, steps, warmup, dist=None, capture=None):
+        """capture: handed to the LAST timed step (OutputDump.capture)"""
         for _ in range(warmup):
             self.step()
         self.sync()
@@ -376,8 +398,8 @@ class Workload(object):
             dist.barrier()
         self.sync()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step()
+        for i in range(steps):
+            self.step(capture if i == steps - 1 else None)
         self.sync()
         self.own_elapsed = time.perf_counter() - t0      # this rank's own work, before it waits for the others
         if dist is not None:
@@ -431,6 +453,50 @@ class Workload(object):
         self.model.close()
         self.model.ctx.close()
         self.dev_frames = None
+
+
+class OutputDump(object):
+    """--dump-outputs DIR: what a caller of the timed path receives from its LAST timed step -- per frame the fp32 logits
+    (B, 19, H, W) and the uint8 labels (B, H, W) the model leaves in its output buffers -- written as float32 .npy files after the
+    timing, so that two builds can be compared output for output (the inputs are a pure function of the arguments).
+
+    capture(t) runs inside that step, right after frame t's plan is enqueued: stream-ordered device-to-device copies on the
+    library's compute stream (accel_model_read) of every clip's labels and of clip 0's logits (a prefix of the buffer, 19 x H x W
+    floats); the step's last frame leaves every clip's logits in the buffer anyway.  The files hold a fixed sample of S pixels
+    (the same seeded positions in every map, all of them when H x W <= S), S sized so that the three stay under 64 MB:
+      logits_clip0.npy       (interval, 19, S)   clip 0, every frame of the step
+      logits_last_frame.npy  (B, 19, S)          every clip, the step's last frame
+      labels.npy             (interval, B, S)    every clip, every frame (class ids as float32)"""
+
+    BUDGET = 48 << 20
+    SEED = 20261016
+
+    def __init__(self, wl, path):
+        import torch
+        self.wl, self.path = wl, path
+        B, H, W, T = wl.B, wl.H, wl.W, wl.interval
+        per_pixel = 4 * (T * 19 + B * 19 + T * B)
+        S = min(H * W, max(1, self.BUDGET // per_pixel))
+        self.pixels = np.sort(np.random.default_rng(self.SEED).choice(H * W, S, replace=False)) if S < H * W else np.arange(H * W)
+        self.logits0 = [torch.empty((19, H * W), dtype=torch.float32, device="cuda") for _ in range(T)]
+        self.labels = [torch.empty((B, H * W), dtype=torch.uint8, device="cuda") for _ in range(T)]
+
+    def capture(self, t):
+        m = self.wl.model
+        m.read_device("logits", self.logits0[t].data_ptr(), self.logits0[t].numel() * 4)
+        m.read_device("labels", self.labels[t].data_ptr(), self.labels[t].numel())
+
+    def write(self):
+        """after Workload.timed (which has synchronised): the captured maps and the last frame's logits, sampled, to disk"""
+        wl, px = self.wl, self.pixels
+        os.makedirs(self.path, exist_ok=True)
+        last = wl.model.read("logits", (wl.B, 19, wl.H * wl.W))
+        arrays = {"logits_clip0": np.stack([x.cpu().numpy()[:, px] for x in self.logits0]),
+                  "logits_last_frame": np.ascontiguousarray(last[:, :, px]),
+                  "labels": np.stack([x.cpu().numpy()[:, px] for x in self.labels]).astype(np.float32)}
+        for name, arr in arrays.items():
+            np.save(os.path.join(self.path, name + ".npy"), arr.astype(np.float32, copy=False))
+        return sorted(arrays)
 
 
 def _pmc_traffic(version, H, W, interval, dtype, B):
@@ -638,11 +704,11 @@ def _run(a):
     gather_failures = []
     _step = wl.step
 
-    def guarded_step():
+    def guarded_step(capture=None):
         if wd is not None:
             wd.beat()
         try:
-            _step()
+            _step(capture)
         except Exception as e:
             if wl.gather is None or world > 1:
                 # N > 1: no rank may carry on without a collective the others still issue -- say what happened and end the job
@@ -652,14 +718,18 @@ def _run(a):
             # one rank (--force-dist on a single GPU): the measurement goes on without the gather and the record says so
             wl.gather = None
             gather_failures.append(repr(e))
-            _step()
+            _step(capture)
     wl.step = guarded_step
 
+    dump = OutputDump(wl, a.dump_outputs) if a.dump_outputs and rank == 0 else None
+    capture = dump.capture if dump is not None else None
     if wd is not None:
         with wd.phase("timed steps", max(a.watchdog, 60.0)):
-            elapsed = wl.timed(a.steps, a.warmup, dist)
+            elapsed = wl.timed(a.steps, a.warmup, dist, capture)
     else:
-        elapsed = wl.timed(a.steps, a.warmup, dist)
+        elapsed = wl.timed(a.steps, a.warmup, dist, capture)
+    if dump is not None:
+        dump.write()
     rank_ms = None
     if dist is not None:
         # every rank's own time for the K steps (between the two barriers a rank that finishes early waits in the second one, so
@@ -675,7 +745,7 @@ def _run(a):
     # N > 1: the same steps once more with the OTHER payload of the gather (uint8 label maps are 76x smaller than fp32
     # logits), so the line shows what the collective costs; and the rate each peer's xGMI link to the root carries
     gather_detail = None
-    if world > 1 and a.gather in ("scores", "logits", "labels") and wl.gather is not None and not gather_failures:
+    if a.full and world > 1 and a.gather in ("scores", "logits", "labels") and wl.gather is not None and not gather_failures:
         other = "logits" if payload != "logits" else "labels"
         try:
             wl.sync()
@@ -752,11 +822,11 @@ def _run(a):
         wd.close()
     if rank == 0 and rank_ms is not None:
         out["rank_ms_per_step"] = rank_ms
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         out["roofline"] = pair_traffic(wl.conv_roofline(a.dtype), *_pmc_traffic(a.version, H, W, a.interval, a.dtype, B))
 
-    # ---- secondary measurements, same harness (single GPU, headline configuration only) ----------------------------------
-    if rank == 0 and world == 1 and dist is None and a.secondary == "auto" and headline_cfg:
+    # ---- secondary measurements (--full), same harness (single GPU, headline configuration only) --------------------------
+    if rank == 0 and a.full and world == 1 and dist is None and a.secondary == "auto" and headline_cfg:
         sec = {}
         steps2, warm2 = max(2, a.steps // 2), 1
 
@@ -871,7 +941,7 @@ def _run(a):
         out["secondary"] = sec
     else:
         wl.close()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.version, a.interval, H, W)
 
     def finish():

@@ -9,8 +9,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with gpurun / on the GPU box)")
     config.addinivalue_line("markers", "gpu_extra: GPU robustness tests beyond the parity rows of SURVEY.md 8 (more bindings, more aspect ratios, more models of a "
-                                       "property another parametrisation already covers): NOT selected by `-m gpu` -- the driver's GPU step has a time limit of 1200 s (round 6: `-m gpu` 420 tests in 849-924 s by box, "
-                                       "`-m gpu_extra` 16 tests in 282 s) --, run them with `-m gpu_extra` (or `-m \"gpu or gpu_extra\"`)")
+                                       "property another parametrisation already covers): they carry the gpu mark too and run under `-m gpu` like every GPU test; "
+                                       "`-m gpu_extra` selects them alone")
 
 
 _TEST_TUNE = os.path.join(os.path.dirname(__file__), "golden", "gfx950_tests.tune")
@@ -47,20 +47,6 @@ def pytest_terminal_summary(terminalreporter, exitstatus, config):
                                     "suite table: %s)" % (replayed, timed, shipped, os.environ.get("ACCEL_TUNE_CACHE", "none")))
     except Exception:
         pass
-
-
-def pytest_collection_modifyitems(config, items):
-    """`-m gpu` means the parity suite: tests that carry gpu_extra (a pytest.param mark or a decorator, beside the module's gpu mark) are left out
-    unless the mark expression names gpu_extra itself."""
-    expr = config.getoption("markexpr", "") or ""
-    if "gpu_extra" in expr:
-        return
-    keep, drop = [], []
-    for it in items:
-        (drop if it.get_closest_marker("gpu_extra") is not None else keep).append(it)
-    if drop and "gpu" in expr:
-        config.hook.pytest_deselected(items=drop)
-        items[:] = keep
 
 
 @pytest.fixture(scope="session")
