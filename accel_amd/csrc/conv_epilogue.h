@@ -149,10 +149,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                float v = acc[i][j][e] * a + b;
-                if (rbase + i * 32 + (e & 3) + 8 * (e >> 2) >= p.M) v = 0.f;
+                const bool in = rbase + i * 32 + (e & 3) + 8 * (e >> 2) < p.M;
+                const float v = in ? acc[i][j][e] * a + b : 0.f;
                 mj = fmaxf(mj, fmaxf(v, v * c));
-                mj2 = fmaxf(mj2, fmaxf(v, v * d) * sc2[j] + sf2[j]);
+                // (a row past M stores nothing: it must not count as v = 0 either -- that is relu(shift2) in the second output)
+                mj2 = fmaxf(mj2, in ? fmaxf(v, v * d) * sc2[j] + sf2[j] : 0.f);
             }
         if (cok[j]) {
             const unsigned bb = __builtin_bit_cast(unsigned, mj), b2 = __builtin_bit_cast(unsigned, mj2);

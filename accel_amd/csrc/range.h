@@ -9,7 +9,10 @@
 // layer must not meet on one word; spread over 1024 words on different lines they cost nothing.  The maximum is order-independent:
 // the slot's content is a function of the tensor alone.
 // Fold: a one-block kernel (misc.hip range_fold_kernel) in front of the first reader after a write takes the maximum of the partial
-// words into word 0.
+// words into word 0.  The partial words are cleared once per run, not per fold: a write that OVERWRITES values a reader has already
+// folded leaves their maximum in the slot, which is then a bound, not the tensor's maximum (the lowering writes every buffer before
+// its first read and never overwrites it afterwards; tests/test_range_slots_gpu.py checks a second fold over another channel range).
+// The other intended bound: a deconvolution whose output is cropped (odd sizes) counts the cropped rows (conv_epilogue.h).
 // Reader: ONE scalar load, then the power of two that puts the largest pixel into [2^13, 2^14): 4x of headroom to the largest half
 // (the Winograd kernels spend it on their input transform's growth), full relative precision (two half terms, 22-23 bits) for every
 // pixel down to 2^-17 of the largest.  (Measured on the way here, same-box A/B of the headline, scripts/ab_round.sh: readers that took

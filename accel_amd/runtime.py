@@ -373,6 +373,13 @@ class Plan(object):
                 out[name.value.decode()] = (s.value, int(src.value))
         return out
 
+    def range_words(self, i):
+        """diagnostics (accel_plan_op_range_words): the words of conv op i's input range slot after the last run, as uint32 --
+        word 0 is what the convolution read, the partial words the writers raise follow (csrc/range.h)"""
+        out = np.zeros(1088, np.uint32)
+        check(lib().accel_plan_op_range_words(self.handle, int(i), _fp(out), out.size))
+        return out
+
     def expand_scores(self, scores_ptr, n_images, logits_ptr, labels_ptr, comm=None):
         """accel_expand_scores: logits + labels of n_images score maps (device pointers) by this plan's own last launch"""
         check(lib().accel_expand_scores(self.handle, ctypes.c_void_p(scores_ptr), int(n_images), ctypes.c_void_p(logits_ptr), ctypes.c_void_p(labels_ptr),
