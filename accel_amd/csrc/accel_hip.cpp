@@ -450,8 +450,12 @@ static void pack_bf16x3r(const std::vector<float>& packed, int classes, int rows
 
 // fp16x2 form of the same fragment-ordered planes (ConvParams::wh2r): every weight as hi + lo, two half terms of w * 2^q[row], the
 // exponent q[row] chosen so that the largest weight of the output channel (over all parity classes) lands in [2^14, 2^15) -- the
-// top of the half range, where lo keeps its full 11 bits for every weight down to 2^-16 of the channel's largest (below that the
-// absolute error is 2^-25, i.e. 2^-39 of the largest).  qexp receives q per row; the epilogue scale is multiplied by 2^-q (exact).
+// top of the half range, where lo keeps its full 11 bits (the pair: 2^-23 relative) for every weight down to 2^-16 of the channel's
+// largest; below that the absolute error is 2^-25 of the scaled value, i.e. 2^-39 to 2^-40 of the largest: a bit lost per octave
+// (tests/test_h2_model_cpu.py; on the device, half subnormals included: tests/test_h2_octaves_gpu.py).  The Winograd planes
+// (conv_wino_b3_pack_h2) split U = G g G^T the same way, one octave higher, because they pay that absolute error at 16 positions
+// against |V| <= 4 max|x|.
+// qexp receives q per row; the epilogue scale is multiplied by 2^-q (exact).
 static void pack_h2r(const std::vector<float>& packed, int classes, int rows, int K_pad, std::vector<uint16_t>& out, size_t plane, std::vector<int>& qexp)
 {
     const int steps = K_pad / 32;

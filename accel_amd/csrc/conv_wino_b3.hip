@@ -579,8 +579,13 @@ void conv_wino_b3_pack(const float* w, int Cout, int Cin, int rows, std::vector<
         }
 }
 
-// The fp16x2 form of the same planes (ConvParams::wubh): U * 2^q[k] as hi + lo, two half terms, q[k] putting the largest |U| of output
-// channel k into [2^14, 2^15) (see pack_h2r in accel_hip.cpp); qexp receives q per row.
+// The fp16x2 form of the same planes (ConvParams::wubh): U * 2^q[k] as hi + lo, two half terms (see pack_h2r in accel_hip.cpp), q[k]
+// putting the largest |U| of output channel k into [2^15, 65504] -- the last octave of the half range; [2^14, 2^15) where it would
+// round past the largest half.  One octave higher than the direct planes: a U term more than 2^-17 below its channel's largest has
+// the absolute error 2^-25 of the scaled value, and the Winograd form pays that at 16 positions against |V| <= 4 max|x| where the
+// direct form pays it at 9 taps against |x|; with the octave that is 2 to 3 times the direct form's error there, without it 4 to 5
+// times (tests/test_h2_octaves_gpu.py test_weight_ladder).  The products stay far inside fp32: |V hi| <= 2^14 at the
+// quarter scale.  qexp receives q per row.
 void conv_wino_b3_pack_h2(const float* w, int Cout, int Cin, int rows, std::vector<unsigned short>& out, std::vector<int>& qexp)
 {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
@@ -604,7 +609,12 @@ void conv_wino_b3_pack_h2(const float* w, int Cout, int Cin, int rows, std::vect
                     amax = std::max(amax, std::fabs(f));
                 }
         }
-        if (amax > 0.f && std::isfinite(amax)) { int e; std::frexp(amax, &e); qexp[k] = 15 - e; }
+        if (amax > 0.f && std::isfinite(amax)) {
+            int e;
+            std::frexp(amax, &e);
+            qexp[k] = 16 - e;
+            if (std::ldexp(amax, qexp[k]) > 65504.f) qexp[k] = 15 - e;      // would round to a half infinity
+        }
         for (int c = 0; c < Cin; ++c)
             for (int pos = 0; pos < 16; ++pos) {
                 const float v = std::ldexp(U[(size_t)c * 16 + pos], qexp[k]);

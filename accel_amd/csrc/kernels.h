@@ -63,7 +63,8 @@ struct ConvParams {
     const void* wub;       // conv_wino_b3.hip: U = G g G^T as three bf16 planes [plane][C/16][16][wino_rows][16]; null: not offered
     unsigned wub_bytes;
     // fp16x2 form of the bf16x3 kernels ("h2", ConvParams::f16 == 3 inside the launchers): every fp32 operand as hi + lo, two half
-    // terms (hi = RTNE(v), lo = RTNE(v - hi): 22-23 significant bits), THREE v_mfma_f32_32x32x16_f16 products per multiply-add
+    // terms (hi = RTNE(v), lo = RTNE(v - hi): 22-23 significant bits for a value within 2^-16 of the largest of its tensor / output
+    // channel, a bit less per octave below that: range.h, tests/h2_model.py), THREE v_mfma_f32_32x32x16_f16 products per multiply-add
     // (hi*hi + hi*lo + lo*hi), fp32 accumulate.  Operands are centred in the half range by exact powers of two: the weights per
     // output channel on the host (folded into scale_h2), the pixels by the power of two that the kernel derives IN ITS PROLOGUE from
     // the largest |pixel| of its input tensor -- measured in the same run by whoever produced that tensor (range slots, below) --

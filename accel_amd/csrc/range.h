@@ -14,8 +14,13 @@
 // its first read and never overwrites it afterwards; tests/test_range_slots_gpu.py checks a second fold over another channel range).
 // The other intended bound: a deconvolution whose output is cropped (odd sizes) counts the cropped rows (conv_epilogue.h).
 // Reader: ONE scalar load, then the power of two that puts the largest pixel into [2^13, 2^14): 4x of headroom to the largest half
-// (the Winograd kernels spend it on their input transform's growth), full relative precision (two half terms, 22-23 bits) for every
-// pixel down to 2^-17 of the largest.  (Measured on the way here, same-box A/B of the headline, scripts/ab_round.sh: readers that took
+// (the Winograd kernels spend it on their input transform's growth).  What a pixel keeps depends on how far below the largest it lies
+// (tests/h2_model.py, asserted per octave in tests/test_h2_model_cpu.py and on the device in tests/test_h2_octaves_gpu.py): the two
+// half terms carry it to 2^-23 relative down to 2^-15 of the largest (2^-16 when the largest sits at the top of its window), to 2^-22
+// one octave further down, and lose a bit per octave from there (2^-17 of the largest: 2^-21 ... 2^-24: 2^-14) -- the unit of lo has
+// reached the half subnormals' 2^-24.  That far it rests on half subnormals surviving the loaders' conversion and the A/B inputs of
+// v_mfma_f32_32x32x16_f16; both keep them on gfx950 (measured: the kernels are the model to 1.3e-7 of sum|w||x| at every octave; a
+// unit that flushed them would lose a bit per octave from 2^-5 of the largest on).  (Measured on the way here, same-box A/B of the headline, scripts/ab_round.sh: readers that took
 // the maximum over 32 spread sub-slots themselves cost 4.3 ms of a 62 ms step as scalar loads -- 32 serialised scalar-cache misses
 // per CU and launch -- and 20 % on the short-K layers as one vector load per lane; writers whose bookkeeping was woven into the store
 // loop cost 30-40 registers per lane and a resident block.)

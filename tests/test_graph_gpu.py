@@ -458,19 +458,13 @@ def test_stale_feature_handle_is_never_read_silently(demo_cfg):
         tester.release_models()
 
 
-# (inside `-m gpu` the same statement is made at the headline size: test_configs_gpu.py test_config4_batch8_1024x2048_equals_eight_single_clip_runs)
-@pytest.mark.parametrize("version", [pytest.param("18", marks=pytest.mark.gpu_extra), "101"])
-def test_batched_clips_match_single_clip_runs(demo_cfg, version):
-    """Throughput mode: every call runs one frame of each of B independent clips (arrays with a leading batch of B).
-    Image b of the batched run must reproduce the batch-1 run of clip b (same kernels, other tile choices: compared
-    at 1e-4 of the logit range; labels identical outside the tie band) -- over a key frame and two non-key frames, so
-    the per-image feature / featG hand-off is covered too."""
+def _batched_against_single_clip_runs(demo_cfg, version, clips, images, H, W, interval):
+    """one batched runner over `clips` against a batch-1 runner per clip; the images of `images` are compared"""
     from accel_amd import demo, mx
     from accel_amd.core import tester
-    H, W, B, interval = 128, 256, 3, 3
+    B = len(clips)
     demo_cfg.SCALES[0] = (H, W)
     arg, aux = synth.model_params(version, H, W, demo_cfg)
-    clips = [synth.make_clip(H, W, interval, seed=77 + b) for b in range(B)]
     per_clip = [demo.build_batches(c, demo_cfg) for c in clips]
     try:
         single = []
@@ -485,7 +479,7 @@ def test_batched_clips_match_single_clip_runs(demo_cfg, version):
             logits, labels = rb.step(t, arrays, interval)
             lg, lab = logits.asnumpy(), labels.asnumpy()
             assert lg.shape == (B, 19, H, W) and lab.shape == (B, H, W)
-            for b in range(B):
+            for b in images:
                 ref = single[b][t][0]
                 tol = 1e-4 * max(1.0, float(np.abs(ref).max()))
                 assert float(np.abs(lg[b] - ref).max()) <= tol, (version, t, b, float(np.abs(lg[b] - ref).max()), tol)
@@ -494,6 +488,34 @@ def test_batched_clips_match_single_clip_runs(demo_cfg, version):
                 np.testing.assert_array_equal(lab[b][safe], np.argmax(ref, axis=0)[safe])
     finally:
         tester.release_models()
+
+
+# (inside `-m gpu` the same statement is made at the headline size: test_configs_gpu.py test_config4_batch8_1024x2048_equals_eight_single_clip_runs)
+@pytest.mark.parametrize("version", [pytest.param("18", marks=pytest.mark.gpu_extra), "101"])
+def test_batched_clips_match_single_clip_runs(demo_cfg, version):
+    """Throughput mode: every call runs one frame of each of B independent clips (arrays with a leading batch of B).
+    Image b of the batched run must reproduce the batch-1 run of clip b (same kernels, other tile choices: compared
+    at 1e-4 of the logit range; labels identical outside the tie band) -- over a key frame and two non-key frames, so
+    the per-image feature / featG hand-off is covered too."""
+    H, W, interval = 128, 256, 3
+    _batched_against_single_clip_runs(demo_cfg, version, [synth.make_clip(H, W, interval, seed=77 + b) for b in range(3)], range(3), H, W, interval)
+
+
+def _maximum_contrast_clip(H, W, n_frames, block=16, dx=2, dy=1):
+    """uint8 frames of 0 / 255 blocks (all three channels alike), translating like synth.make_clip: the largest activations an 8-bit
+    input can cause"""
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = ((((yy // block) + (xx // block)) % 2) * 255).astype(np.uint8)
+    return [np.repeat(np.roll(base, (dy * t, dx * t), axis=(0, 1))[:, :, None], 3, axis=2) for t in range(n_frames)]
+
+
+def test_a_maximum_contrast_clip_does_not_cost_its_batch_neighbours_their_accuracy(demo_cfg):
+    """test_batched_clips_match_single_clip_runs with the last of the three clips replaced by blocks of 0 and 255.  Every fp16x2 layer
+    takes its pixel scale from the largest |activation| of the whole batch (csrc/range.h), so in the batched run images 0 and 1 are
+    split at the scale the third clip sets: they must still meet, against their own single-clip runs, the bar of that test."""
+    H, W, interval = 128, 256, 3
+    clips = [synth.make_clip(H, W, interval, seed=77 + b) for b in range(2)] + [_maximum_contrast_clip(H, W, interval)]
+    _batched_against_single_clip_runs(demo_cfg, "101", clips, (0, 1), H, W, interval)
 
 
 @pytest.mark.parametrize("version,key_interval", [("18", 5), ("101", 3), ("50", 5), ("34", 3)])
