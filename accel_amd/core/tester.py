@@ -26,7 +26,7 @@ import numpy as np
 
 from .. import lower as _lower
 from .. import runtime
-from ..mx.ndarray import DeviceArray
+from ..mx.ndarray import DeviceArray, RawFrames
 
 _MODELS = {}   # (device id, N, H, W, parameter token, owner) -> runtime.Model: the key and cur plans of one demo share buffers
 
@@ -205,14 +205,17 @@ class Predictor(object):
                     ptr, _ = m.buffer("data_key")
                     m.read_device("data", ptr, N * 3 * H * W * 4)
                 else:
-                    m.write("data_key", _host(arrays["data_key"]))
+                    _write_image(m, "data_key", arrays["data_key"])
                 res["data_key"] = tag
         tag = _uid(arrays["data"])
         if tag is None or res.get("data") != tag:
             if tag is not None and pre.get("data") == tag:
-                m.commit("data")
+                if isinstance(data, RawFrames):      # its BYTES were prefetched (uint8 shadow): converted on the way into `data`
+                    m.commit_u8("data", *_u8_layout(data), **data.geometry)
+                else:
+                    m.commit("data")
             else:
-                m.write("data", _host(arrays["data"]))
+                _write_image(m, "data", data)
             res["data"] = tag
         pre.pop("data", None)
         for name in self._data_names:          # further image inputs (data_ref of the training graphs)
@@ -287,13 +290,17 @@ class Predictor(object):
         self._model.write("feat", np.ascontiguousarray(f.transpose(0, 2, 3, 1)))
 
     def prefetch(self, data_array):
-        """Announce the NEXT call's `data` input: a page-locked array (mx.nd.array(.., ctx=mx.cpu_pinned())) starts
+        """Announce the NEXT call's `data` input: a page-locked array (mx.nd.array(.., ctx=mx.cpu_pinned()), or raw uint8 frames
+        built with mx.nd.raw_frames(.., ctx=mx.cpu_pinned())) starts
         crossing PCIe on the copy stream now, beside the running forward; the next predict() that receives this very
         array takes it from the shadow buffer.  Anything else is ignored (uploaded at predict time as usual)."""
         pb = getattr(data_array, "pinned", None)
         if pb is None or self._model is None:
             return False
-        self._model.prefetch("data", pb)
+        if isinstance(data_array, RawFrames):       # uint8 frames: a quarter of the bytes cross PCIe, into a shadow of their own
+            self._model.prefetch_u8("data", pb)
+        else:
+            self._model.prefetch("data", pb)
         self._model.__dict__.setdefault("_prefetched", {})["data"] = data_array.uid
         return True
 
@@ -309,6 +316,21 @@ class Predictor(object):
 def _uid(a):
     """content identity of an input array: DeviceArrays are immutable, raw numpy inputs have none (always uploaded)"""
     return getattr(a, "uid", None)
+
+
+def _u8_layout(raw):
+    """(n, h, w, pitch, means) of a RawFrames array, as Model.commit_u8 takes them"""
+    n, h, w = raw.frames.shape[:3]
+    return n, h, w, 3 * w, raw.means
+
+
+def _write_image(m, buf, arr):
+    """an image input that is not in HBM yet: raw uint8 frames are uploaded as bytes and resized / centred / padded by the GPU
+    (accel_model_write_u8), anything else is the fp32 tensor itself"""
+    if isinstance(arr, RawFrames):
+        m.write_u8(buf, arr.frames, arr.means, **arr.geometry)
+    else:
+        m.write(buf, _host(arr))
 
 
 def _host(a):

@@ -93,6 +93,12 @@ struct accel_model {
     std::map<std::string, uint64_t> generation;     // write generation per persistent buffer (accel_model_buffer_generation)
     struct Shadow { void* ptr = nullptr; size_t bytes = 0, filled = 0; hipEvent_t ready = nullptr, consumed = nullptr; bool was_consumed = false; };
     std::map<std::string, Shadow> shadows;          // prefetch targets (accel_model_prefetch / accel_model_commit)
+    // uint8 frames (accel_model_write_u8 / accel_model_prefetch_u8 / accel_model_commit_u8): the bytes of a frame wait in HBM for the
+    // conversion kernel -- per buffer in a uint8 shadow of its own, never the fp32 shadow above (a prefetch of one kind cannot be
+    // committed as the other), or in the one staging buffer of synchronous host writes
+    std::map<std::string, Shadow> shadows_u8;
+    void* stage_u8 = nullptr;
+    size_t stage_u8_bytes = 0;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;
@@ -1635,6 +1641,8 @@ extern "C" int accel_model_destroy(accel_model* m)
     for (accel_plan* p : m->plans) plan_free(p);
     for (auto& kv : m->pbufs) { hipFree(kv.second.ptr); if (kv.second.slot) hipFree(const_cast<void**>(kv.second.slot)); }
     for (auto& kv : m->shadows) { if (kv.second.ready) hipEventDestroy(kv.second.ready); if (kv.second.consumed) hipEventDestroy(kv.second.consumed); hipFree(kv.second.ptr); }
+    for (auto& kv : m->shadows_u8) { if (kv.second.ready) hipEventDestroy(kv.second.ready); if (kv.second.consumed) hipEventDestroy(kv.second.consumed); hipFree(kv.second.ptr); }
+    if (m->stage_u8) hipFree(m->stage_u8);
     delete m;
     return 0;
 }
@@ -2018,6 +2026,135 @@ extern "C" int accel_model_commit(accel_model* m, const char* buf)
     HIP_TRY(hipStreamWaitEvent(m->ctx->stream, sh->second.ready, 0));
     if (int rc = unbind(m, m->pbufs[buf])) return rc;
     HIP_TRY(launch_copy_bytes(sh->second.ptr, m->pbufs[buf].ptr, sh->second.filled, m->ctx->stream));
+    HIP_TRY(hipEventRecord(sh->second.consumed, m->ctx->stream));
+    sh->second.was_consumed = true;
+    sh->second.filled = 0;
+    m->source_written(buf);
+    return 0;
+}
+
+// ---- uint8 frames ---------------------------------------------------------------------------------------------------------------
+// Geometry of a uint8 frame conversion, checked before anything is enqueued: every message names the argument at fault.
+static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
+                         int H, int W)
+{
+    if (!bgr) return fail(ACCEL_ERR_ARG, "%s: bgr is NULL", fn);
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (h < 1) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be >= 1", fn, h);
+    if (w < 1) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be >= 1", fn, w);
+    if (pitch < (size_t)3 * w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %zu", fn, pitch, w, (size_t)3 * w);
+    if (!(step > 0.0) || step > 1e9) return fail(ACCEL_ERR_ARG, "%s: step = %g, must be a positive number of source pixels per output pixel", fn, step);
+    if (H < 1 || W < 1) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be >= 1", fn, H, W);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    if (step == 1.0 && (out_h != h || out_w != w))
+        return fail(ACCEL_ERR_ARG, "%s: step = 1 copies the frame, but out_h x out_w = %d x %d is not h x w = %d x %d", fn, out_h, out_w, h, w);
+    return 0;
+}
+
+static int frame_u8_buf(const char* fn, accel_model* m, const char* buf, int n, int H, int W, DevBuf** out)
+{
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "%s: unknown buffer '%s'", fn, buf);
+    const size_t need = (size_t)n * 3 * H * W * 4;
+    if (need != it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n x 3 x H x W fp32 = %d x 3 x %d x %d = %zu bytes, buffer '%s' has %zu", fn, n, H, W, need, buf, it->second.bytes);
+    *out = &it->second;
+    return 0;
+}
+
+extern "C" int accel_frame_u8(accel_ctx* ctx, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                              int out_h, int out_w, double step, int H, int W, float* out)
+{
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_u8: NULL argument");
+    if (int rc = frame_u8_args("accel_frame_u8", bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t sb = (size_t)n * h * pitch, ob = (size_t)n * 3 * H * W * 4;
+    unsigned char* s = nullptr;
+    float* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&s, sb));
+    if (hipMalloc((void**)&d, ob) != hipSuccess) { hipFree(s); return fail(ACCEL_ERR_HIP, "accel_frame_u8: hipMalloc of %zu bytes failed", ob); }
+    int rc = 0;
+    if (hipMemcpy(s, bgr, sb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_u8: H2D copy failed");
+    if (!rc && launch_frames_u8(s, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, d, ctx->stream) != hipSuccess)
+        rc = fail(ACCEL_ERR_HIP, "accel_frame_u8: launch failed");
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_u8: sync failed");
+    if (!rc && hipMemcpy(out, d, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_u8: D2H copy failed");
+    hipFree(s); hipFree(d);
+    return rc;
+}
+
+extern "C" int accel_model_write_u8(accel_model* m, const char* buf, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                                    int out_h, int out_w, double step, int H, int W, int src_on_device)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_u8: NULL argument");
+    if (int rc = frame_u8_args("accel_model_write_u8", bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf("accel_model_write_u8", m, buf, n, H, W, &b)) return rc;
+    const unsigned char* src = bgr;
+    if (!src_on_device) {
+        const size_t sb = (size_t)n * h * pitch;
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        if (m->stage_u8_bytes < sb) {
+            // (hipFree waits for the device: no conversion kernel is still reading the old staging buffer)
+            if (m->stage_u8) { HIP_TRY(hipFree(m->stage_u8)); m->stage_u8 = nullptr; m->stage_u8_bytes = 0; }
+            HIP_TRY(hipMalloc(&m->stage_u8, sb));
+            m->stage_u8_bytes = sb;
+        }
+        HIP_TRY(hipMemcpyAsync(m->stage_u8, bgr, sb, hipMemcpyHostToDevice, m->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(m->ctx->stream));   // pageable source may be reused by the caller
+        src = static_cast<const unsigned char*>(m->stage_u8);
+    }
+    if (int rc = unbind(m, *b)) return rc;
+    HIP_TRY(launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(b->ptr), m->ctx->stream));
+    m->source_written(buf);
+    return 0;
+}
+
+extern "C" int accel_model_prefetch_u8(accel_model* m, const char* buf, const void* pinned_src, size_t bytes)
+{
+    if (!m || !buf || !pinned_src) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: unknown buffer '%s'", buf);
+    if (!bytes) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: bytes = 0");
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    accel_model::Shadow& sh = m->shadows_u8[buf];
+    if (!sh.ready) {
+        HIP_TRY(hipEventCreateWithFlags(&sh.ready, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&sh.consumed, hipEventDisableTiming));
+    }
+    if (sh.bytes < bytes) {
+        // frames of another size: a larger shadow (hipFree waits for the device, so for the kernel that read the old one)
+        if (sh.ptr) { HIP_TRY(hipFree(sh.ptr)); sh.ptr = nullptr; sh.bytes = 0; }
+        HIP_TRY(hipMalloc(&sh.ptr, bytes));
+        sh.bytes = bytes;
+    } else if (sh.was_consumed) {
+        // the previous commit's kernel read the shadow on the compute stream: do not overwrite under it
+        HIP_TRY(hipStreamWaitEvent(m->ctx->copy, sh.consumed, 0));
+    }
+    HIP_TRY(hipMemcpyAsync(sh.ptr, pinned_src, bytes, hipMemcpyHostToDevice, m->ctx->copy));
+    HIP_TRY(hipEventRecord(sh.ready, m->ctx->copy));
+    sh.filled = bytes;
+    return 0;
+}
+
+extern "C" int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, const double* means_bgr,
+                                     int out_h, int out_w, double step, int H, int W)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: unknown buffer '%s'", buf);
+    auto sh = m->shadows_u8.find(buf);
+    if (sh == m->shadows_u8.end() || !sh->second.filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_u8_args("accel_model_commit_u8", sh->second.ptr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf("accel_model_commit_u8", m, buf, n, H, W, &b)) return rc;
+    if ((size_t)n * h * pitch > sh->second.filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: n x h x pitch = %d x %d x %zu bytes, %zu were prefetched for '%s'", n, h, pitch, sh->second.filled, buf);
+    HIP_TRY(hipStreamWaitEvent(m->ctx->stream, sh->second.ready, 0));
+    if (int rc = unbind(m, *b)) return rc;
+    HIP_TRY(launch_frames_u8(static_cast<const unsigned char*>(sh->second.ptr), n, h, w, pitch, means_bgr, out_h, out_w, step, H, W,
+                             static_cast<float*>(b->ptr), m->ctx->stream));
     HIP_TRY(hipEventRecord(sh->second.consumed, m->ctx->stream));
     sh->second.was_consumed = true;
     sh->second.filled = 0;

@@ -147,6 +147,11 @@ hipError_t launch_prep_rgb(const float* src, float* dst, int H, int W,
 hipError_t launch_prep_flow(const float* cur, const float* prev, float* dst, int H, int W,
                             int N, hipStream_t st, const float* const* cur_slot = nullptr, const float* const* prev_slot = nullptr, unsigned* yr = nullptr);
 hipError_t launch_set_slot(const void** slot, const void* value, hipStream_t st);
+// uint8 frames (frames_u8.hip): n frames of h x w x 3 BGR bytes, `pitch` bytes per row and h * pitch per frame, in device memory -> n x 3 x H x W
+// fp32 planar RGB (the layout of `data`): bilinear resize by `step` source pixels per output pixel into out_h x out_w (step == 1: the
+// bytes themselves, out_h == h and out_w == w), mean removed in float64, padding = fp32(-mean); bit for bit utils/image.py
+hipError_t launch_frames_u8(const unsigned char* src, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
+                            int H, int W, float* dst, hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

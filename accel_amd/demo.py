@@ -65,20 +65,25 @@ def get_symbols(version, cfg):
     return inst, inst.get_key_test_symbol(cfg), inst.get_cur_test_symbol(cfg)
 
 
-def build_batches(frames_bgr, cfg, pinned=False):
+def build_batches(frames_bgr, cfg, pinned=False, raw=False):
     """demo.py:165-190: list of [data, data_key, feat_key] arrays per frame.
 
     One array per frame serves as this frame's `data` and as the next frame's `data_key` (the reference builds two
     NDArrays from the same image, demo.py:176-181): arrays are immutable, so the Predictor recognises the object it
     uploaded one call earlier and copies the image inside HBM instead of sending it over PCIe twice.
-    pinned=True places the images in page-locked memory (mx.cpu_pinned()), the source of overlapped uploads."""
+    pinned=True places the images in page-locked memory (mx.cpu_pinned()), the source of overlapped uploads.
+    raw=True keeps every frame as its uint8 BGR bytes (mx.nd.raw_frames): no fp32 image is built on the host, a quarter of
+    the bytes cross PCIe and the GPU resizes, removes the mean and pads (accel_model_write_u8)."""
     data, prev = [], None
     ctx = mx.cpu_pinned() if pinned else None
     zero_feat = mx.nd.array(np.zeros((1, cfg.network.DFF_FEAT_DIM, 1, 1)))
     for im in frames_bgr:
-        target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
-        im, _ = resize(im, target_size, max_size, stride=cfg.network.IMAGE_STRIDE)
-        cur = mx.nd.array(transform(im, cfg.network.PIXEL_MEANS), ctx=ctx)
+        if raw:
+            cur = mx.nd.raw_frames(im, cfg, ctx=ctx)
+        else:
+            target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
+            im, _ = resize(im, target_size, max_size, stride=cfg.network.IMAGE_STRIDE)
+            cur = mx.nd.array(transform(im, cfg.network.PIXEL_MEANS), ctx=ctx)
         if prev is None:
             prev = cur
         data.append([cur, prev, zero_feat])
@@ -170,6 +175,9 @@ def main(argv=None):
     ap.add_argument('--pageable', action='store_true',
                     help='frames in pageable host memory, uploaded synchronously inside each forward (the reference\'s '
                          'loop one to one); default: page-locked frames, the next frame\'s upload overlaps the current forward')
+    ap.add_argument('--raw-frames', dest='raw_frames', action='store_true',
+                    help='upload the frames as uint8 BGR bytes and resize / mean-subtract / pad them on the GPU: no fp32 image '
+                         'is built on the host')
     args = ap.parse_args(argv)
     version, interv, num_ex = str(args.version), args.interval, args.num_ex
     if version not in ['18', '34', '50', '101', 'dff']:
@@ -205,6 +213,9 @@ def main(argv=None):
 
     from .utils import load_model, synth
     H, W = frames[0].shape[:2]
+    if args.raw_frames:       # the size the graphs are bound at: the frame after resize + padding
+        from .utils.image import resize_geometry
+        H, W = resize_geometry(H, W, config.SCALES[0][0], config.SCALES[0][1], config.network.IMAGE_STRIDE)[3:]
     if args.params:
         arg_params, aux_params = {}, {}
         for prefix in args.params:
@@ -215,7 +226,7 @@ def main(argv=None):
         print('no --params given: seeded random weights (throughput is valid, mIoU is meaningless)')
         arg_params, aux_params = synth.model_params(version, H, W, config)
 
-    data = build_batches(frames, config, pinned=not args.pageable)
+    data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames)
     runner = ClipRunner(version, config, arg_params, aux_params, (H, W))
     for j in range(min(2, len(data))):       # warm up (demo.py:207-220)
         runner.step(j, data[j], interv)[1].asnumpy()

@@ -67,6 +67,68 @@ def array(src, ctx=None, dtype=np.float32):
     return DeviceArray(host=np.array(a, dtype=dtype, order="C", copy=True))
 
 
+class RawFrames(DeviceArray):
+    """Video frames as a camera, a decoder or a PNG gives them -- uint8 N x h x w x 3, BGR -- standing for the image tensor the
+    graphs read: `.shape` is the (N, 3, H, W) of transform(resize(frame)) (lib/utils/image.py:194-235), and a Predictor
+    uploads the BYTES (a quarter of the fp32 tensor) and has the GPU resize, remove the mean and pad
+    (accel_model_write_u8 / _prefetch_u8 / _commit_u8).  `.asnumpy()` is that tensor computed on the host, lazily, so a
+    consumer that knows nothing about raw frames still works.  All frames of one array have the same size."""
+
+    def __init__(self, frames_bgr_u8, pixel_means, target_size, max_size, stride=0, ctx=None):
+        from ..utils import image
+        if isinstance(frames_bgr_u8, (list, tuple)):
+            if len({np.shape(f) for f in frames_bgr_u8}) != 1:
+                raise ValueError("all frames of one raw-frame array must have the same size")
+            frames_bgr_u8 = np.stack([np.asarray(f) for f in frames_bgr_u8])
+        a = np.asarray(frames_bgr_u8)
+        if a.ndim == 3:
+            a = a[None]
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError("raw frames must be uint8 N x h x w x 3 (BGR), got %s %s" % (a.dtype, a.shape))
+        n, h, w = a.shape[:3]
+        pb = None
+        if ctx is not None and getattr(ctx, "device_type", "") == "cpu_pinned":
+            from .. import runtime
+            pb = runtime.PinnedBuffer(a.shape, np.uint8)
+            pb.array[...] = a
+            frames = pb.array
+        else:
+            frames = np.array(a, order="C", copy=True)      # a copy, like mx.nd.array: later edits of the source do not reach it
+        frames.setflags(write=False)
+        scale, out_h, out_w, H, W = image.resize_geometry(h, w, target_size, max_size, stride)
+        DeviceArray.__init__(self, shape=(n, 3, H, W), fetch=self._host_tensor, pinned=pb)
+        self.frames = frames
+        self.means = tuple(float(v) for v in np.asarray(pixel_means, np.float64).reshape(-1))
+        self.resize_args = (target_size, max_size, stride)
+        self.scale = scale
+        # what the C ABI is told (include/accel_hip.h, uint8 video frames)
+        self.geometry = dict(out_h=out_h, out_w=out_w, step=image.resample_step(h, w, scale, out_h, out_w), H=H, W=W)
+
+    def _host_tensor(self):
+        from ..utils import image
+        t, m, s = self.resize_args
+        return np.concatenate([image.transform(image.resize(f, t, m, stride=s)[0], self.means) for f in self.frames]).astype(np.float32)
+
+    @property
+    def on_device(self):
+        return False
+
+    @property
+    def has_host_copy(self):
+        return True
+
+    def __repr__(self):
+        return "<RawFrames %s uint8 for %s>" % ("x".join(map(str, self.frames.shape)), "x".join(map(str, self._shape)))
+
+
+def raw_frames(frames_bgr_u8, cfg, ctx=None):
+    """Raw uint8 BGR frames (one h x w x 3 frame, N x h x w x 3, or a list of frames of one size) for a Predictor, resized
+    to cfg.SCALES[0], centred on cfg.network.PIXEL_MEANS and padded to cfg.network.IMAGE_STRIDE on the GPU.  Always a COPY
+    of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
+    target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
+    return RawFrames(frames_bgr_u8, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, ctx=ctx)
+
+
 def zeros(shape, ctx=None, dtype=np.float32):
     return DeviceArray(host=np.zeros(shape, dtype))
 

@@ -73,6 +73,10 @@ def _declare(lib):
         "accel_model_prefetch": [vp, c.c_char_p, vp, sz],
         "accel_model_commit": [vp, c.c_char_p],
         "accel_model_read_async": [vp, c.c_char_p, vp, sz],
+        "accel_frame_u8": [vp, vp, i, i, i, sz, vp, i, i, c.c_double, i, i, vp],
+        "accel_model_write_u8": [vp, c.c_char_p, vp, i, i, i, sz, vp, i, i, c.c_double, i, i, i],
+        "accel_model_prefetch_u8": [vp, c.c_char_p, vp, sz],
+        "accel_model_commit_u8": [vp, c.c_char_p, i, i, i, sz, vp, i, i, c.c_double, i, i],
         "accel_comm_available": [],
         "accel_comm_unique_id": [vp],
         "accel_comm_create": [vp, i, i, vp, c.POINTER(vp)],
@@ -155,6 +159,30 @@ def _fp(a):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _u8_frames(frames, width=None):
+    """uint8 frames as the C ABI takes them: (contiguous array, n, h, w, pitch).  `frames` is n x h x w x 3 (or one h x w x 3
+    frame), or -- with `width` -- n x h x pitch bytes: rows of `width` BGR pixels followed by padding bytes."""
+    a = np.ascontiguousarray(frames, dtype=np.uint8)
+    if width is not None:
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("pitched frames must be n x h x pitch bytes, got shape %s" % (a.shape,))
+        return a, a.shape[0], a.shape[1], int(width), a.shape[2]
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4 or a.shape[3] != 3:
+        raise ValueError("frames must be n x h x w x 3 uint8 (BGR), got shape %s" % (a.shape,))
+    return a, a.shape[0], a.shape[1], a.shape[2], 3 * a.shape[2]
+
+
+def _means3(means_bgr):
+    m = [float(v) for v in np.asarray(means_bgr, np.float64).reshape(-1)]
+    if len(m) != 3:
+        raise ValueError("means_bgr must hold three values (B, G, R)")
+    return (ctypes.c_double * 3)(*m)
 
 
 class Context(object):
@@ -250,6 +278,15 @@ class Context(object):
         labels = np.empty((1, H, W), np.uint8)
         check(lib().accel_argmax_c(self.handle, _fp(logits), C, H, W, _fp(labels)))
         return labels
+
+    def frame_u8(self, frames, means_bgr, out_h, out_w, step, H, W, width=None):
+        """accel_frame_u8: uint8 BGR frames (see _u8_frames) -> the n x 3 x H x W fp32 tensor transform(resize(..)) gives on the
+        host; out_h, out_w, step, H, W from utils.image.resize_geometry / resample_step"""
+        a, n, h, w, pitch = _u8_frames(frames, width)
+        out = np.empty((n, 3, int(H), int(W)), np.float32)
+        check(lib().accel_frame_u8(self.handle, _fp(a), n, h, w, pitch, _means3(means_bgr), int(out_h), int(out_w), float(step),
+                                   int(H), int(W), _fp(out)))
+        return out
 
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
@@ -474,6 +511,30 @@ class Model(object):
     def commit(self, buf):
         self.__dict__.get("_resident", {}).pop(buf, None)
         check(lib().accel_model_commit(self.handle, buf.encode()))
+
+    def write_u8(self, buf, frames, means_bgr, out_h, out_w, step, H, W, width=None):
+        """accel_model_write_u8: host uint8 BGR frames (see _u8_frames) converted on the GPU into the image input `buf`"""
+        a, n, h, w, pitch = _u8_frames(frames, width)
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_u8(self.handle, buf.encode(), _fp(a), n, h, w, pitch, _means3(means_bgr), int(out_h), int(out_w),
+                                         float(step), int(H), int(W), 0))
+
+    def write_u8_device(self, buf, dev_ptr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W):
+        """the same with the bytes already in HBM (a decoder's output, a torch uint8 tensor's data_ptr()): read in place; the
+        caller keeps them unchanged until the kernel has run"""
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_u8(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), int(h), int(w), int(pitch),
+                                         _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W), 1))
+
+    def prefetch_u8(self, buf, pinned):
+        """enqueue the upload of a uint8 PinnedBuffer into the uint8 shadow of `buf` on the copy stream"""
+        check(lib().accel_model_prefetch_u8(self.handle, buf.encode(), pinned.ptr, pinned.nbytes))
+
+    def commit_u8(self, buf, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W):
+        """accel_model_commit_u8: the compute stream waits for prefetch_u8, then the kernel converts the shadow into `buf`"""
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_commit_u8(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), _means3(means_bgr),
+                                          int(out_h), int(out_w), float(step), int(H), int(W)))
 
     def read_async(self, buf, pinned):
         """enqueue the download of `buf` into a PinnedBuffer on the compute stream; valid after ctx.sync()"""

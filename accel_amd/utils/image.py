@@ -50,6 +50,29 @@ def resize(im, target_size, max_size, stride=0):
     return canvas, scale
 
 
+def resize_geometry(rows, cols, target_size, max_size, stride=0):
+    """The geometry `resize` would produce for a rows x cols frame, WITHOUT resampling anything: (scale, out_h, out_w, H, W) --
+    the scale `resize` returns, the size of the resized image and the size after padding to the stride (H, W = out_h, out_w
+    when stride == 0).  The same expressions as `resize`, so the uint8 route of the library (accel_frame_u8, which is told
+    out_h, out_w and the step instead of deriving them) and the host path cannot disagree about a rounding."""
+    rows, cols = int(rows), int(cols)
+    short, long_ = (rows, cols) if rows <= cols else (cols, rows)
+    scale = float(target_size) / float(short)
+    if np.round(scale * long_) > max_size:
+        scale = float(max_size) / float(long_)
+    out_h, out_w = (int(round(rows * scale)), int(round(cols * scale))) if scale != 1.0 else (rows, cols)
+    if stride == 0:
+        return scale, out_h, out_w, out_h, out_w
+    up = lambda n: -(-n // stride) * stride
+    return scale, out_h, out_w, up(out_h), up(out_w)
+
+
+def resample_step(rows, cols, scale, out_h, out_w):
+    """Source pixels per output pixel of the resize `resize` performs: 1 / scale -- and exactly 1.0 where it copies the frame,
+    which is at scale 1 and ALSO where the rounded size equals the frame's (`_resize_bilinear` returns its input then)."""
+    return 1.0 if scale == 1.0 or (int(out_h), int(out_w)) == (int(rows), int(cols)) else 1.0 / scale
+
+
 def transform(im, pixel_means):
     """Contract of lib/utils/image.py:224-235: a BGR H x W x 3 frame becomes the 1 x 3 x H x W RGB tensor with the per-channel
     mean removed (`pixel_means` is given in B, G, R order like the frame).  float64 like the reference; arrays become fp32

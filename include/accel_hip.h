@@ -166,6 +166,40 @@ int accel_model_prefetch(accel_model* m, const char* buf, const void* pinned_src
 int accel_model_commit(accel_model* m, const char* buf);
 int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes);
 
+/* ---- uint8 video frames ---------------------------------------------------------------------------------------------
+ * A camera, a decoder or a PNG gives uint8 h x w x 3 BGR; the image inputs are fp32 n x 3 x H x W RGB, mean-subtracted
+ * and padded (lib/utils/image.py:194-235, resize + transform -- numpy float64 on one host thread in the reference's
+ * harness, and 4x the bytes of the frame over PCIe afterwards).  Here the bytes are uploaded as they are and one kernel
+ * (csrc/frames_u8.hip) writes the fp32 tensor, bit for bit what accel_amd/utils/image.py computes on the host:
+ *   bgr, n, h, w, pitch   n frames of h rows of w pixels, 3 bytes each in B, G, R order; `pitch` bytes from row to row
+ *                         (>= 3 * w) and h * pitch bytes from frame to frame
+ *   means_bgr             three float64 means in B, G, R order (PIXEL_MEANS): value = fp32(double(grey) - mean), ONE rounding
+ *   out_h, out_w, step    the resized image and the source pixels per output pixel (1 / scale) of the bilinear resize
+ *                         (half-pixel centres, float64, rounded to a grey level like the host's uint8 resize); step == 1
+ *                         copies the bytes and needs out_h == h, out_w == w.  The CALLER derives the three from the resize
+ *                         rule (utils/image.py resize_geometry): the library does not re-derive it, so two `round`
+ *                         implementations cannot disagree
+ *   H, W                  the padded size (out_h <= H, out_w <= W); padding holds fp32(0 - mean), not 0: the reference
+ *                         pads with zeros BEFORE it removes the mean
+ * Argument errors return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_frame_u8           operator level: host bytes in, host tensor out (the parity tests)
+ *   accel_model_write_u8     accel_model_write for uint8 frames into an image input `buf` of n x 3 x H x W fp32: host bytes go
+ *                            through a library-owned uint8 staging buffer on the compute stream (src_on_device = 0), device
+ *                            bytes -- a frame a GPU decoder left in HBM -- are read in place (src_on_device = 1: the caller keeps
+ *                            them unchanged until the kernel has run).  Ends a zero-copy binding and bumps the write
+ *                            generation exactly as accel_model_write does
+ *   accel_model_prefetch_u8  accel_model_prefetch for uint8 bytes: page-locked `pinned_src` crosses PCIe on the copy stream
+ *                            into a uint8 shadow of `buf` -- a shadow of its own, not the fp32 one of accel_model_prefetch
+ *   accel_model_commit_u8    the compute stream waits for that upload, then the kernel converts the shadow into `buf`
+ *                            (n * h * pitch <= the bytes prefetched) */
+int accel_frame_u8(accel_ctx* ctx, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                   int out_h, int out_w, double step, int H, int W, float* out);
+int accel_model_write_u8(accel_model* m, const char* buf, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                         int out_h, int out_w, double step, int H, int W, int src_on_device);
+int accel_model_prefetch_u8(accel_model* m, const char* buf, const void* pinned_src, size_t bytes);
+int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, const double* means_bgr,
+                          int out_h, int out_w, double step, int H, int W);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
