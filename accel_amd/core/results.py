@@ -1,0 +1,118 @@
+"""Finishing a frame on the GPU: the label map `mx.nd.argmax(logits)` returns, taken back to the source frame's size there and handed
+over as labels, as a colour image or as counts in a confusion matrix (csrc/results_u8.hip behind accel_model_labels_to_source /
+_labels_colour / _hist_add / _hist_read).
+
+The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
+evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
+padded, resized size H x W a network fed with raw frames is bound at (mx.nd.raw_frames), the ground truth and the viewer are at the
+camera's h x w, and `RawFrames.geometry` says how to get back.
+
+A label handle names a buffer, not a copy: its `device_ref` is (model, "labels", write generation).  Every function here checks that
+generation first -- stale labels are never read."""
+import numpy as np
+
+from .. import runtime
+
+
+def _geometry(handle, like, hw=None):
+    """(n, out_h, out_w, h, w) of a finishing call.  `like`: a RawFrames array (its frames' size and the resize it stands for), a
+    dict with out_h, out_w and h, w (other keys, such as those of RawFrames.geometry, are ignored; h, w default to `hw`), or None:
+    the whole H x W map is valid and is resized to `hw`."""
+    shape = tuple(handle.shape)
+    if len(shape) != 3:
+        raise ValueError("a label handle is n x H x W, got shape %s" % (shape,))
+    n, H, W = shape
+    if like is None:
+        out_h, out_w, src = H, W, hw or (H, W)
+    elif isinstance(like, dict):
+        out_h, out_w = like["out_h"], like["out_w"]
+        src = (like["h"], like["w"]) if "h" in like and "w" in like else hw
+        if src is None:
+            raise ValueError("the geometry dict has no source size: add h and w")
+    else:
+        out_h, out_w = like.geometry["out_h"], like.geometry["out_w"]
+        src = tuple(like.frames.shape[1:3])
+    if hw is not None and tuple(hw) != tuple(src):
+        raise ValueError("the ground truth is %d x %d, the source frames are %d x %d" % (hw[0], hw[1], src[0], src[1]))
+    return n, int(out_h), int(out_w), int(src[0]), int(src[1])
+
+
+def _model(handle):
+    """the model whose `labels` buffer the handle stands for -- still holding what the handle was made for, or AccelError"""
+    ref = getattr(handle, "device_ref", None)
+    if not ref or ref[1] != "labels":
+        raise runtime.AccelError("not a label handle of the GPU path (mx.nd.argmax of a Predictor's logits): nothing to finish on the GPU")
+    m, buf, gen = ref
+    if m.generation(buf) != gen:
+        raise runtime.AccelError("this label handle is stale: its buffer has been written since (fetch it with .asnumpy(), or finish "
+                                 "the frame, before the next forward that writes labels)")
+    return m
+
+
+def labels_at_source(handle, like):
+    """The labels of `handle` at the source frames' size: numpy n x h x w uint8 (utils.image.labels_to_source_host, on the GPU)."""
+    m = _model(handle)
+    n, out_h, out_w, h, w = _geometry(handle, like)
+    return m.labels_to_source(n, out_h, out_w, h, w)
+
+
+def colour(handle, like, palette, frames=None, alpha=256, rgb=True):
+    """The labels of `handle` as a colour image at the source frames' size: numpy n x h x w x 3 uint8, palette[label] (256 x 3 R, G, B)
+    in R, G, B order (rgb=True) or B, G, R; blended over `frames` (uint8 n x h x w x 3 BGR; frames=True takes those of a RawFrames
+    `like`) with weight alpha / 256 (utils.image.colour_host, on the GPU)."""
+    m = _model(handle)
+    n, out_h, out_w, h, w = _geometry(handle, like)
+    if frames is True:
+        frames = like.frames
+    return m.labels_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
+
+
+def per_class_iu(hist):
+    """demo.py:55-56"""
+    hist = np.asarray(hist, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.diag(hist) / (hist.sum(1) + hist.sum(0) - np.diag(hist))
+
+
+class Evaluator(object):
+    """mIoU bookkeeping of the demo loop (fast_hist per frame, summed) with the counting on the GPU: `add` enqueues one kernel that
+    takes the prediction to the ground truth's size and adds to a confusion matrix that lives in the model; nothing but the ground
+    truth crosses PCIe until `hist()`.  One accumulator per model: the evaluator adopts the model of the first handle it is given
+    and reports what was added since then (the accumulator's content at that moment is its zero)."""
+
+    def __init__(self, num_classes):
+        self.num_classes = int(num_classes)
+        if not 1 <= self.num_classes <= 32:
+            raise ValueError("num_classes = %d, must be in 1 .. 32" % self.num_classes)
+        self._m = None
+        self._base = np.zeros((self.num_classes, self.num_classes), np.int64)
+
+    def add(self, handle, gt, like=None):
+        """count `handle`'s labels against ground truth `gt` ([n x] h x w uint8; ids >= num_classes, such as 255, are ignored)"""
+        m = _model(handle)
+        if self._m is None:
+            self._base = m.hist_read(self.num_classes).astype(np.int64)
+            self._m = m
+        elif m is not self._m:
+            raise runtime.AccelError("this evaluator accumulates in another model: one Evaluator per model")
+        g = np.asarray(gt)
+        if g.ndim == 2:
+            g = g[None]
+        if g.dtype != np.uint8:
+            g = np.where((g >= 0) & (g < 256), g, 255).astype(np.uint8)      # anything outside a byte is ignored either way
+        n, out_h, out_w, h, w = _geometry(handle, like, hw=g.shape[1:3])
+        if g.shape[0] != n:
+            raise ValueError("%d label maps but %d ground-truth maps" % (n, g.shape[0]))
+        m.hist_add(g, out_h, out_w, self.num_classes)
+
+    def hist(self, clear=False):
+        """the confusion matrix so far: int64 num_classes x num_classes, rows ground truth, columns prediction (waits for the GPU)"""
+        if self._m is None:
+            return np.zeros((self.num_classes, self.num_classes), np.int64)
+        out = self._m.hist_read(self.num_classes, clear=clear).astype(np.int64) - self._base
+        if clear:
+            self._base[...] = 0
+        return out
+
+    def per_class_iu(self):
+        return per_class_iu(self.hist())

@@ -99,6 +99,14 @@ struct accel_model {
     std::map<std::string, Shadow> shadows_u8;
     void* stage_u8 = nullptr;
     size_t stage_u8_bytes = 0;
+    // finished frames (accel_model_labels_to_source / _hist_add / _hist_read / _labels_colour): the shape of `labels` (the score_tail op
+    // of a plan, or a `meta labels_n= labels_h= labels_w=` line, says it), a staging buffer for results on their way to the host, and the
+    // confusion matrix: 32 x 32 unsigned 64-bit words that persist across calls, for ncls = hist_ncls classes (0: empty since the last clear)
+    int labels_n = 0, labels_h = 0, labels_w = 0;
+    void* stage_out = nullptr;
+    size_t stage_out_bytes = 0;
+    unsigned long long* hist = nullptr;
+    int hist_ncls = 0;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;
@@ -331,6 +339,7 @@ static int parse_plan(accel_plan* p, const char* text)
         }
         if (kind == "meta") {
             if (kv_has(kv, "feat_c")) { p->m->feat_c = (int)kv_int(kv, "feat_c"); p->m->feat_h = (int)kv_int(kv, "feat_h"); p->m->feat_w = (int)kv_int(kv, "feat_w"); p->m->feat_n = (int)kv_int(kv, "feat_n", 1); }
+            if (kv_has(kv, "labels_h")) { p->m->labels_n = (int)kv_int(kv, "labels_n", 1); p->m->labels_h = (int)kv_int(kv, "labels_h"); p->m->labels_w = (int)kv_int(kv, "labels_w"); }
             continue;
         }
         if (kind == "arena") { p->arena_bytes = strtoull(kv_str(kv, "bytes", "0").c_str(), nullptr, 10); continue; }
@@ -1005,6 +1014,7 @@ static int finalize_op(accel_plan* p, Op& op)
         q.left = op.a.ptr; q.lCs = op.a.Cs; q.Hs = op.a.H; q.Ws = op.a.W;
         q.H = (int)kv_int(kv, "H"); q.W = (int)kv_int(kv, "W");
         if (q.H != 16 * q.Hs || q.W != 16 * q.Ws) return fail(ACCEL_ERR_PLAN, "score_tail: output must be 16x the score map");
+        if (op.d.space == "labels") { p->m->labels_n = op.d.N; p->m->labels_h = q.H; p->m->labels_w = q.W; }      // what the finishing calls read
         q.logits = op.c.ptr; q.labels = reinterpret_cast<unsigned char*>(op.d.ptr);
         const size_t wn = (size_t)q.ncls * 32 * 32;
         if ((rc = upload_param(p, kv_str(kv, "wl"), wn, &q.wl))) return rc;
@@ -1643,6 +1653,8 @@ extern "C" int accel_model_destroy(accel_model* m)
     for (auto& kv : m->shadows) { if (kv.second.ready) hipEventDestroy(kv.second.ready); if (kv.second.consumed) hipEventDestroy(kv.second.consumed); hipFree(kv.second.ptr); }
     for (auto& kv : m->shadows_u8) { if (kv.second.ready) hipEventDestroy(kv.second.ready); if (kv.second.consumed) hipEventDestroy(kv.second.consumed); hipFree(kv.second.ptr); }
     if (m->stage_u8) hipFree(m->stage_u8);
+    if (m->stage_out) hipFree(m->stage_out);
+    if (m->hist) hipFree(m->hist);
     delete m;
     return 0;
 }
@@ -2159,6 +2171,264 @@ extern "C" int accel_model_commit_u8(accel_model* m, const char* buf, int n, int
     sh->second.was_consumed = true;
     sh->second.filled = 0;
     m->source_written(buf);
+    return 0;
+}
+
+// ---- finished frames: labels at the source size, confusion matrix, colour image (results_u8.hip) ---------------------------------------
+// Geometry shared by the three, checked before anything is enqueued: every message names the argument at fault.
+static int results_args(const char* fn, int n, int H, int W, int out_h, int out_w, int h, int w)
+{
+    const int lim = 32768;       // the kernels index with 32-bit products of two sizes
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (H < 1 || W < 1 || H > lim || W > lim) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be in 1 .. %d", fn, H, W, lim);
+    if (h < 1 || h > lim) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be in 1 .. %d", fn, h, lim);
+    if (w < 1 || w > lim) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be in 1 .. %d", fn, w, lim);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    return 0;
+}
+
+static int pitch_arg(const char* fn, const char* name, size_t pitch, int w, int bytes_per_pixel)
+{
+    if (pitch < (size_t)bytes_per_pixel * w)
+        return fail(ACCEL_ERR_ARG, "%s: %s = %zu bytes, a row of w = %d pixels has %zu", fn, name, pitch, w, (size_t)bytes_per_pixel * w);
+    return 0;
+}
+
+static int ncls_arg(const char* fn, int ncls)
+{
+    if (ncls < 1 || ncls > 32) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be in 1 .. 32", fn, ncls);
+    return 0;
+}
+
+static int alpha_arg(const char* fn, int alpha)
+{
+    if (alpha < 0 || alpha > 256) return fail(ACCEL_ERR_ARG, "%s: alpha = %d, must be in 0 .. 256", fn, alpha);
+    return 0;
+}
+
+// rows of `row` bytes, `pitch` apart on the host, tightly packed in device memory: only the bytes of the rows are written
+static hipError_t rows_to_host(void* dst, size_t pitch, const void* dev, size_t row, size_t rows, hipStream_t st)
+{
+    if (pitch == row) return hipMemcpyAsync(dst, dev, row * rows, hipMemcpyDeviceToHost, st);
+    return hipMemcpy2DAsync(dst, pitch, dev, row, row, rows, hipMemcpyDeviceToHost, st);
+}
+
+// device temporaries of the operator-level entry points
+struct DevTemps {
+    std::vector<void*> ptrs;
+    ~DevTemps() { for (void* p : ptrs) hipFree(p); }
+    void* get(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr; ptrs.push_back(p); return p; }
+    void* upload(const void* host, size_t bytes) { void* p = get(bytes); if (p && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
+};
+
+extern "C" int accel_labels_to_source(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                                      uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_labels_to_source";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w));
+    if (!l || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_source(l, n, H, W, out_h, out_w, h, w, d, (size_t)w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_labels_hist(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w,
+                                 const uint8_t* gt, int h, int w, size_t gt_pitch, int ncls, uint64_t* hist)
+{
+    const char* fn = "accel_labels_hist";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    if (!hist) return fail(ACCEL_ERR_ARG, "%s: hist is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const size_t hb = (size_t)ncls * ncls * sizeof(uint64_t);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* g = static_cast<const unsigned char*>(t.upload(gt, (size_t)n * h * gt_pitch));
+    unsigned long long* d = static_cast<unsigned long long*>(t.upload(hist, hb));
+    if (!l || !g || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_hist(l, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, d, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hist, d, hb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_labels_colour(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                                   const uint8_t* palette_rgb, int rgb_order, const uint8_t* frame_bgr, size_t frame_pitch, int alpha,
+                                   uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_labels_colour";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* f = frame_bgr ? static_cast<const unsigned char*>(t.upload(frame_bgr, (size_t)n * h * frame_pitch)) : nullptr;
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w * 3));
+    if (!l || !d || (frame_bgr && !f)) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_colour(l, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, (size_t)3 * w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)3 * w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// the model's label maps: the `labels` buffer and the shape the plans write it in
+static int model_labels(const char* fn, accel_model* m, int n, const unsigned char** labels)
+{
+    auto it = m->pbufs.find("labels");
+    if (it == m->pbufs.end() || m->labels_h < 1 || m->labels_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: this model has no `labels` buffer of a known shape (no plan with a score_tail op is bound)", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (n > m->labels_n || (size_t)n * m->labels_h * m->labels_w > it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %d", fn, n, m->labels_n);
+    *labels = static_cast<const unsigned char*>(it->second.ptr);
+    return 0;
+}
+
+// host bytes on their way to a kernel (ground truth, a frame to blend with): the staging buffer of the uint8 frames, grown on demand
+static int stage_in(accel_model* m, const void* host, size_t bytes, const unsigned char** dev)
+{
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (m->stage_u8_bytes < bytes) {
+        // (hipFree waits for the device: no kernel is still reading the old staging buffer)
+        if (m->stage_u8) { HIP_TRY(hipFree(m->stage_u8)); m->stage_u8 = nullptr; m->stage_u8_bytes = 0; }
+        HIP_TRY(hipMalloc(&m->stage_u8, bytes));
+        m->stage_u8_bytes = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(m->stage_u8, host, bytes, hipMemcpyHostToDevice, m->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));   // pageable source may be reused by the caller
+    *dev = static_cast<const unsigned char*>(m->stage_u8);
+    return 0;
+}
+
+static int stage_out(accel_model* m, size_t bytes, unsigned char** dev)
+{
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (m->stage_out_bytes < bytes) {
+        if (m->stage_out) { HIP_TRY(hipFree(m->stage_out)); m->stage_out = nullptr; m->stage_out_bytes = 0; }
+        HIP_TRY(hipMalloc(&m->stage_out, bytes));
+        m->stage_out_bytes = bytes;
+    }
+    *dev = static_cast<unsigned char*>(m->stage_out);
+    return 0;
+}
+
+extern "C" int accel_model_labels_to_source(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_labels_to_source";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        HIP_TRY(launch_labels_source(labels, n, H, W, out_h, out_w, h, w, dst, dst_pitch, st));
+        return 0;
+    }
+    unsigned char* d = nullptr;
+    if (int rc = stage_out(m, (size_t)n * h * w, &d)) return rc;
+    HIP_TRY(launch_labels_source(labels, n, H, W, out_h, out_w, h, w, d, (size_t)w, st));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device)
+{
+    const char* fn = "accel_model_hist_add";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (m->hist_ncls && m->hist_ncls != ncls)
+        return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the accumulator holds counts of %d classes since its last clear", fn, ncls, m->hist_ncls);
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (!m->hist) {
+        HIP_TRY(hipMalloc((void**)&m->hist, 32 * 32 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(m->hist, 0, 32 * 32 * sizeof(unsigned long long), st));
+    }
+    const unsigned char* g = gt;
+    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
+    HIP_TRY(launch_labels_hist(labels, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, m->hist, st));
+    m->hist_ncls = ncls;
+    return 0;
+}
+
+extern "C" int accel_model_hist_read(accel_model* m, uint64_t* out, int ncls, int clear)
+{
+    const char* fn = "accel_model_hist_read";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!out) return fail(ACCEL_ERR_ARG, "%s: out is NULL", fn);
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (m->hist_ncls && m->hist_ncls != ncls)
+        return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the accumulator holds counts of %d classes since its last clear", fn, ncls, m->hist_ncls);
+    const size_t hb = (size_t)ncls * ncls * sizeof(uint64_t);
+    if (!m->hist || !m->hist_ncls) { memset(out, 0, hb); return 0; }      // nothing added since the last clear
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, m->hist, hb, hipMemcpyDeviceToHost, st));
+    if (clear) {
+        HIP_TRY(hipMemsetAsync(m->hist, 0, 32 * 32 * sizeof(unsigned long long), st));
+        m->hist_ncls = 0;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_labels_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_labels_colour";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    hipStream_t st = m->ctx->stream;
+    const unsigned char* f = frame_bgr;
+    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
+    if (dst_on_device) {
+        HIP_TRY(launch_labels_colour(labels, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, dst, dst_pitch, st));
+        return 0;
+    }
+    unsigned char* d = nullptr;
+    if (int rc = stage_out(m, (size_t)n * h * w * 3, &d)) return rc;
+    HIP_TRY(launch_labels_colour(labels, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, (size_t)3 * w, st));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)3 * w, (size_t)n * h, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 

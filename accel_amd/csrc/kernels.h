@@ -152,6 +152,17 @@ hipError_t launch_set_slot(const void** slot, const void* value, hipStream_t st)
 // bytes themselves, out_h == h and out_w == w), mean removed in float64, padding = fp32(-mean); bit for bit utils/image.py
 hipError_t launch_frames_u8(const unsigned char* src, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
                             int H, int W, float* dst, hipStream_t st);
+// finished frames (results_u8.hip): n label maps of H x W bytes (valid region out_h x out_w, top left) taken to the source size h x w by the
+// integer nearest rule labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)] -- as labels (rows `dst_pitch` apart), as counts added
+// to an ncls x ncls matrix of 64-bit words (rows gt, columns prediction, ids >= ncls ignored; ncls <= 32), or as n x h x w x 3 colours
+// palette_rgb[label] (768 host bytes; rgb_order 1 = R, G, B, 0 = B, G, R), blended with a BGR frame when one is given and alpha < 256.
+// All pointers but palette_rgb are device memory; the kernels only read `labels`
+hipError_t launch_labels_source(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,
+                                hipStream_t st);
+hipError_t launch_labels_hist(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, const unsigned char* gt, int h, int w, size_t gt_pitch,
+                              int ncls, unsigned long long* hist, hipStream_t st);
+hipError_t launch_labels_colour(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, const unsigned char* palette_rgb,
+                                int rgb_order, const unsigned char* frame, size_t frame_pitch, int alpha, unsigned char* dst, size_t dst_pitch, hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

@@ -178,6 +178,12 @@ def main(argv=None):
     ap.add_argument('--raw-frames', dest='raw_frames', action='store_true',
                     help='upload the frames as uint8 BGR bytes and resize / mean-subtract / pad them on the GPU: no fp32 image '
                          'is built on the host')
+    ap.add_argument('--finish-on-gpu', dest='finish_on_gpu', action='store_true',
+                    help='finish every frame on the GPU: the timed loop fetches the labels at the SOURCE frame\'s size (padding and '
+                         'resize undone there), the confusion matrix of the mIoU accumulates in HBM and --out writes those labels; '
+                         'with --raw-frames this evaluates frames of any size against ground truth of their own size')
+    ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
+                                                 '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
     version, interv, num_ex = str(args.version), args.interval, args.num_ex
     if version not in ['18', '34', '50', '101', 'dff']:
@@ -211,8 +217,16 @@ def main(argv=None):
             frames += clip
             names += ['synthetic_%06d_%06d_leftImg8bit.png' % (i, t) for t in range(interv)]
 
+    if args.scales:
+        config.SCALES[0] = tuple(int(v) for v in args.scales.split('x'))
     from .utils import load_model, synth
     H, W = frames[0].shape[:2]
+    if args.finish_on_gpu:    # how a label map goes back to a frame: the valid region of the bound size and the frame's own size
+        from .core import results
+        from .utils.image import resize_geometry
+        g = resize_geometry(H, W, config.SCALES[0][0], config.SCALES[0][1], config.network.IMAGE_STRIDE)
+        source = dict(out_h=g[1], out_w=g[2], h=H, w=W)
+        evaluator, hist_before = results.Evaluator(num_classes), np.zeros((num_classes, num_classes), np.int64)
     if args.raw_frames:       # the size the graphs are bound at: the frame after resize + padding
         from .utils.image import resize_geometry
         H, W = resize_geometry(H, W, config.SCALES[0][0], config.SCALES[0][1], config.network.IMAGE_STRIDE)[3:]
@@ -238,7 +252,10 @@ def main(argv=None):
         _, lab = runner.step(idx, arrays, interv)
         if idx + 1 < len(data) and not args.pageable:
             runner.prefetch(data[idx + 1])        # next frame starts crossing PCIe while this one computes
-        pred = np.uint8(np.squeeze(lab.asnumpy()))
+        if args.finish_on_gpu:
+            pred = results.labels_at_source(lab, source)[0]
+        else:
+            pred = np.uint8(np.squeeze(lab.asnumpy()))
         elapsed = toc()
         time_sum += elapsed
         count += 1
@@ -254,8 +271,13 @@ def main(argv=None):
         if lf is not None:
             from PIL import Image
             label = np.asarray(Image.open(lf))
-            curr_hist = fast_hist(pred.flatten(), label.flatten(), num_classes)
-            hist += curr_hist
+            if args.finish_on_gpu:      # counted on the GPU against `lab` itself; this frame's matrix is the difference of two reads
+                evaluator.add(lab, label, like=source)
+                hist = evaluator.hist()
+                curr_hist, hist_before = hist - hist_before, hist
+            else:
+                curr_hist = fast_hist(pred.flatten(), label.flatten(), num_classes)
+                hist += curr_hist
             print('mIoU {mIoU:.3f}'.format(mIoU=round(np.nanmean(per_class_iu(curr_hist)) * 100, 2)))
             print('(cum) mIoU {mIoU:.3f}'.format(mIoU=round(np.nanmean(per_class_iu(hist)) * 100, 2)))
     if hist.sum() > 0:

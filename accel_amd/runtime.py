@@ -77,6 +77,13 @@ def _declare(lib):
         "accel_model_write_u8": [vp, c.c_char_p, vp, i, i, i, sz, vp, i, i, c.c_double, i, i, i],
         "accel_model_prefetch_u8": [vp, c.c_char_p, vp, sz],
         "accel_model_commit_u8": [vp, c.c_char_p, i, i, i, sz, vp, i, i, c.c_double, i, i],
+        "accel_labels_to_source": [vp, vp, i, i, i, i, i, i, i, vp, sz],
+        "accel_labels_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, vp],
+        "accel_labels_colour": [vp, vp, i, i, i, i, i, i, i, vp, i, vp, sz, i, vp, sz],
+        "accel_model_labels_to_source": [vp, i, i, i, i, i, vp, sz, i],
+        "accel_model_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
+        "accel_model_hist_read": [vp, vp, i, i],
+        "accel_model_labels_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
         "accel_comm_available": [],
         "accel_comm_unique_id": [vp],
         "accel_comm_create": [vp, i, i, vp, c.POINTER(vp)],
@@ -185,6 +192,35 @@ def _means3(means_bgr):
     return (ctypes.c_double * 3)(*m)
 
 
+def _u8_maps(maps, width=None, what="labels"):
+    """uint8 maps as the C ABI takes them: (contiguous array, n, h, w, pitch).  `maps` is n x h x w (or one h x w map), or --
+    with `width` -- n x h x pitch bytes: rows of `width` pixels followed by padding bytes."""
+    a = np.ascontiguousarray(maps, dtype=np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("%s must be n x h x w uint8, got shape %s" % (what, a.shape))
+    return a, a.shape[0], a.shape[1], a.shape[2] if width is None else int(width), a.shape[2]
+
+
+def _palette(palette):
+    p = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8).reshape(-1))
+    if p.size != 768:
+        raise ValueError("the palette must hold 256 x 3 bytes (R, G, B), got %d" % p.size)
+    return p
+
+
+def _result_rows(out, n, h, w, channels):
+    """the destination of a finishing call and its row pitch: a fresh n x h x w [x 3] array, or the caller's n x h x pitch bytes
+    (only the first w * channels bytes of every row are written)"""
+    if out is None:
+        out = np.empty((n, h, w) if channels == 1 else (n, h, w, channels), np.uint8)
+        return out, w * channels
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable or out.ndim != 3 or out.shape[:2] != (n, h):
+        raise ValueError("out must be a writeable C-contiguous uint8 array of n x h x pitch = %d x %d x pitch bytes" % (n, h))
+    return out, out.shape[2]
+
+
 class Context(object):
     def __init__(self, device_id=0):
         self.handle = ctypes.c_void_p()
@@ -286,6 +322,39 @@ class Context(object):
         out = np.empty((n, 3, int(H), int(W)), np.float32)
         check(lib().accel_frame_u8(self.handle, _fp(a), n, h, w, pitch, _means3(means_bgr), int(out_h), int(out_w), float(step),
                                    int(H), int(W), _fp(out)))
+        return out
+
+    def labels_to_source(self, labels, out_h, out_w, h, w, out=None):
+        """accel_labels_to_source: n x H x W label maps whose valid region is out_h x out_w -> n x h x w labels at the source size
+        (utils.image.labels_to_source_host); `out`: n x h x pitch bytes to write the rows into instead"""
+        a, n, H, W, _ = _u8_maps(labels)
+        out, pitch = _result_rows(out, n, int(h), int(w), 1)
+        check(lib().accel_labels_to_source(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), int(h), int(w), _fp(out), pitch))
+        return out
+
+    def labels_hist(self, labels, out_h, out_w, gt, ncls, width=None, hist=None):
+        """accel_labels_hist: the confusion matrix (rows gt, columns prediction, uint64 ncls x ncls) of the label maps taken to the
+        size of `gt` (n x h x w, or n x h x pitch bytes with `width`), added to `hist` when one is given"""
+        a, n, H, W, _ = _u8_maps(labels)
+        g, gn, h, w, pitch = _u8_maps(gt, width, "gt")
+        if gn != n:
+            raise ValueError("%d label maps but %d ground-truth maps" % (n, gn))
+        hist = np.zeros((int(ncls), int(ncls)), np.uint64) if hist is None else np.ascontiguousarray(hist, dtype=np.uint64).copy()
+        check(lib().accel_labels_hist(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), _fp(g), h, w, pitch, int(ncls), _fp(hist)))
+        return hist
+
+    def labels_colour(self, labels, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
+        """accel_labels_colour: n x h x w x 3 colours palette[label] at the source size (utils.image.colour_host), blended with
+        `frames` (uint8 BGR, see _u8_frames) when given; `out`: n x h x pitch bytes to write the rows into instead"""
+        a, n, H, W, _ = _u8_maps(labels)
+        f, fp = None, 0
+        if frames is not None:
+            f, fn, fh, fw, fp = _u8_frames(frames, width)
+            if (fn, fh, fw) != (n, int(h), int(w)):
+                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn, fh, fw, n, h, w))
+        out, pitch = _result_rows(out, n, int(h), int(w), 3)
+        check(lib().accel_labels_colour(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)),
+                                        int(bool(rgb)), None if f is None else _fp(f), fp, int(alpha), _fp(out), pitch))
         return out
 
     def flow_input(self, cur, prev):
@@ -535,6 +604,53 @@ class Model(object):
         self.__dict__.get("_resident", {}).pop(buf, None)
         check(lib().accel_model_commit_u8(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), _means3(means_bgr),
                                           int(out_h), int(out_w), float(step), int(H), int(W)))
+
+    # ---- finished frames: they only READ `labels` (no generation changes) ------------------------------------------------------
+    def labels_to_source(self, n, out_h, out_w, h, w, out=None):
+        """accel_model_labels_to_source: the first n maps of `labels` at the source size h x w, as a numpy n x h x w uint8"""
+        out, pitch = _result_rows(out, int(n), int(h), int(w), 1)
+        check(lib().accel_model_labels_to_source(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(out), pitch, 0))
+        return out
+
+    def labels_to_source_device(self, dev_ptr, n, out_h, out_w, h, w, pitch):
+        """the same into caller-owned HBM (enqueued, no host wait)"""
+        check(lib().accel_model_labels_to_source(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), ctypes.c_void_p(dev_ptr), int(pitch), 1))
+
+    def hist_add(self, gt, out_h, out_w, ncls, width=None):
+        """accel_model_hist_add: add the confusion matrix of `labels` against host ground truth (n x h x w uint8, or n x h x pitch
+        bytes with `width`) to the model's accumulator"""
+        g, n, h, w, pitch = _u8_maps(gt, width, "gt")
+        check(lib().accel_model_hist_add(self.handle, _fp(g), n, h, w, pitch, int(out_h), int(out_w), int(ncls), 0))
+
+    def hist_add_device(self, dev_ptr, n, h, w, pitch, out_h, out_w, ncls):
+        """the same with the ground truth already in HBM: read in place, nothing crosses PCIe; the caller keeps it unchanged until
+        the kernel has run"""
+        check(lib().accel_model_hist_add(self.handle, ctypes.c_void_p(dev_ptr), int(n), int(h), int(w), int(pitch), int(out_h), int(out_w), int(ncls), 1))
+
+    def hist_read(self, ncls, clear=False):
+        """accel_model_hist_read: the accumulator as uint64 ncls x ncls (rows gt, columns prediction); clear=True zeroes it"""
+        out = np.zeros((int(ncls), int(ncls)), np.uint64)
+        check(lib().accel_model_hist_read(self.handle, _fp(out), int(ncls), int(bool(clear))))
+        return out
+
+    def labels_colour(self, n, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
+        """accel_model_labels_colour: the first n maps of `labels` as n x h x w x 3 colours at the source size, blended with host
+        `frames` (uint8 BGR, see _u8_frames) when given"""
+        f, fp = None, 0
+        if frames is not None:
+            f, fn, fh, fw, fp = _u8_frames(frames, width)
+            if (fn, fh, fw) != (int(n), int(h), int(w)):
+                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn, fh, fw, n, h, w))
+        out, pitch = _result_rows(out, int(n), int(h), int(w), 3)
+        check(lib().accel_model_labels_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
+                                              None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
+        return out
+
+    def labels_colour_device(self, dst_ptr, n, out_h, out_w, h, w, pitch, palette, frame_ptr=None, frame_pitch=0, alpha=256, rgb=True):
+        """the same into caller-owned HBM, blended with frames that are in HBM already (enqueued, no host wait)"""
+        check(lib().accel_model_labels_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
+                                              ctypes.c_void_p(frame_ptr) if frame_ptr else None, int(frame_pitch), int(alpha), 1,
+                                              ctypes.c_void_p(dst_ptr), int(pitch), 1))
 
     def read_async(self, buf, pinned):
         """enqueue the download of `buf` into a PinnedBuffer on the compute stream; valid after ctx.sync()"""

@@ -73,6 +73,38 @@ def resample_step(rows, cols, scale, out_h, out_w):
     return 1.0 if scale == 1.0 or (int(out_h), int(out_w)) == (int(rows), int(cols)) else 1.0 / scale
 
 
+def nearest_index(dst, src):
+    """The row (or column) of a `src`-pixel map that each of `dst` output rows takes under nearest-neighbour resizing, in integer
+    arithmetic: min(i * src // dst, src - 1).  Equal to the float64 expression of dataset/cityscape._nearest_resize (the
+    reference's evaluator, lib/dataset/cityscape.py:227) for every size pair the tests walk; the form csrc/results_u8.hip computes."""
+    return np.minimum(np.arange(int(dst), dtype=np.int64) * int(src) // int(dst), int(src) - 1)
+
+
+def labels_to_source_host(labels, out_h, out_w, h, w):
+    """The specification of accel_labels_to_source: label maps [n x] H x W whose valid (unpadded) region is out_h x out_w in the
+    top-left corner -- what a network fed with resize(frame) produces -- taken back to the frame's own size h x w: the crop,
+    resized with nearest neighbour.  Undoes `resize` for a label map (RawFrames.geometry holds out_h, out_w)."""
+    a = np.asarray(labels)
+    ys, xs = nearest_index(h, out_h), nearest_index(w, out_w)
+    return np.ascontiguousarray(a[..., :int(out_h), :int(out_w)][..., ys, :][..., xs])
+
+
+def colour_host(labels, palette, frames=None, alpha=256, rgb=True):
+    """The specification of accel_labels_colour: `palette` (256 x 3 R, G, B, flat or not) looked up per label, [n x] h x w x 3 in
+    R, G, B order (rgb=True, what PIL wants) or B, G, R (what the frames are).  With `frames` (uint8 B, G, R of the same size)
+    every channel is (alpha * colour + (256 - alpha) * frame + 128) >> 8, alpha in 0 .. 256; 256 is the pure colour."""
+    if not 0 <= int(alpha) <= 256:
+        raise ValueError("alpha = %r, must be in 0 .. 256" % (alpha,))
+    out = np.asarray(palette, np.uint8).reshape(-1, 3)[np.asarray(labels)]
+    if not rgb:
+        out = out[..., ::-1]
+    if frames is not None and int(alpha) < 256:
+        f = np.asarray(frames, np.uint8)
+        f = f[..., ::-1] if rgb else f
+        out = ((int(alpha) * out.astype(np.int64) + (256 - int(alpha)) * f.astype(np.int64) + 128) >> 8).astype(np.uint8)
+    return np.ascontiguousarray(out)
+
+
 def transform(im, pixel_means):
     """Contract of lib/utils/image.py:224-235: a BGR H x W x 3 frame becomes the 1 x 3 x H x W RGB tensor with the per-channel
     mean removed (`pixel_means` is given in B, G, R order like the frame).  float64 like the reference; arrays become fp32

@@ -200,6 +200,54 @@ int accel_model_prefetch_u8(accel_model* m, const char* buf, const void* pinned_
 int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, const double* means_bgr,
                           int out_h, int out_w, double step, int H, int W);
 
+/* ---- finished frames: labels at the source size, confusion matrix, colour image ------------------------------------
+ * The output side of the loop (demo.py:245-266: `.asnumpy()` of the label map, fast_hist, the palette PNG) on the GPU
+ * (csrc/results_u8.hip).  A label map is n x H x W uint8; its valid (unpadded) region is out_h x out_w in the top-left
+ * corner; the source frame is h x w.  Source pixel (y, x) takes
+ *     labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)]          (integer division)
+ * -- the nearest-neighbour rule of the reference's evaluator (lib/dataset/cityscape.py:227) applied to the cropped
+ * region; a crop or a copy when h x w == out_h x out_w.  out_h, out_w are what accel_model_write_u8 was told.
+ *   labels at the source size   n x h x w uint8, rows `dst_pitch` bytes apart (>= w), h * dst_pitch from frame to frame;
+ *                               bytes between rows are not written
+ *   confusion matrix            hist[gt * ncls + pred] += 1 for every source pixel with gt < ncls and pred < ncls (255 and
+ *                               any other id >= ncls are ignored, as fast_hist of demo.py:50-53 ignores them): rows are
+ *                               ground truth, columns prediction; ncls in 1 .. 32; gt is n x h x w uint8 with `gt_pitch`;
+ *                               unsigned 64-bit counts, exact, independent of the order of arrival
+ *   colour image                n x h x w x 3 uint8 = palette_rgb[label] for a 256 x 3 R, G, B table (768 host bytes, passed
+ *                               to the kernel by value), stored R, G, B (rgb_order = 1: what PIL wants) or B, G, R
+ *                               (rgb_order = 0: what the frames are).  With frame_bgr (n x h x w x 3 B, G, R, `frame_pitch`)
+ *                               every channel is (alpha * colour + (256 - alpha) * frame + 128) >> 8, alpha in 0 .. 256;
+ *                               alpha = 256 or frame_bgr = NULL gives the pure colour
+ * Sizes are at most 32768.  Argument errors (a NULL pointer, a size < 1, out_h > H, out_w > W, a pitch smaller than a row,
+ * ncls outside 1 .. 32, alpha outside 0 .. 256, n larger than the bound batch, ncls other than the accumulator's since its
+ * last clear) return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_labels_to_source, accel_labels_hist, accel_labels_colour
+ *                               operator level: host bytes in, host bytes out (the parity tests); `hist` is ncls * ncls
+ *                               words that are ADDED to
+ *   accel_model_labels_to_source, accel_model_hist_add, accel_model_hist_read, accel_model_labels_colour
+ *                               the same on the model's `labels` buffer (n x H x W as the bound plans write it), enqueued
+ *                               on the context stream after the run that wrote it.  They only read `labels`: no write
+ *                               generation changes, no captured graph is touched.  Host gt / frame bytes go through a
+ *                               library-owned staging buffer (*_on_device = 0), device bytes are read in place (= 1: the
+ *                               caller keeps them unchanged until the kernel has run); a host `dst` is filled when the
+ *                               call returns, a device `dst` (dst_on_device = 1) when the stream reaches it.
+ *                               The confusion matrix accumulates in the model, across calls, until
+ *                               accel_model_hist_read(.., clear = 1); hist_read waits for the stream and copies
+ *                               ncls * ncls words to the host (zeros when nothing was added since the last clear) */
+int accel_labels_to_source(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                           uint8_t* dst, size_t dst_pitch);
+int accel_labels_hist(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w,
+                      const uint8_t* gt, int h, int w, size_t gt_pitch, int ncls, uint64_t* hist);
+int accel_labels_colour(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                        const uint8_t* palette_rgb, int rgb_order, const uint8_t* frame_bgr, size_t frame_pitch, int alpha,
+                        uint8_t* dst, size_t dst_pitch);
+int accel_model_labels_to_source(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device);
+int accel_model_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device);
+int accel_model_hist_read(accel_model* m, uint64_t* out, int ncls, int clear);
+int accel_model_labels_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                              const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                              uint8_t* dst, size_t dst_pitch, int dst_on_device);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
