@@ -1,5 +1,6 @@
 """Hand-written plans for the operator tests: NHWC views of the arena, a builder of plan text (import_nchw -> convolutions -> export_nchw
-with every launch geometry forced) and a float64 convolution.  No tests in here."""
+with every launch geometry forced; or the byte movers of csrc/misc.hip between sub-views of canvases the host writes and reads raw)
+and a float64 convolution.  No tests in here."""
 import numpy as np
 
 al = lambda b: (b + 255) // 256 * 256
@@ -10,20 +11,26 @@ bits = lambda v: int(np.float32(v).view(np.uint32)) & 0x7FFFFFFF
 class V(object):
     """an NHWC view of the arena: offset, channels, channel stride, H, W, images"""
 
-    def __init__(self, off, C, Cs, H, W, N, space="A"):
-        self.off, self.C, self.Cs, self.H, self.W, self.N, self.space = off, C, Cs, H, W, N, space
+    def __init__(self, off, C, Cs, H, W, N, space="A", half=False):
+        self.off, self.C, self.Cs, self.H, self.W, self.N, self.space, self.half = off, C, Cs, H, W, N, space, half
 
     def ref(self):
-        return "%s:%d:%d:%d:%d:%d:%d" % (self.space, self.off, self.C, self.Cs, self.H, self.W, self.N)
+        return "%s:%d:%d:%d:%d:%d:%d%s" % (self.space, self.off, self.C, self.Cs, self.H, self.W, self.N, ":h" if self.half else "")
 
     def sub(self, c0, C):
         return V(self.off + 4 * c0, C, self.Cs, self.H, self.W, self.N, self.space)
+
+    @property
+    def c0(self):
+        """first channel of the view inside its buffer's pixel stride (fp32 views that start in the buffer's first pixel)"""
+        return self.off // 4
 
 
 class Builder(object):
     def __init__(self, N):
         self.N, self.arena, self.head, self.lines, self.params = N, 0, [], [], {}
         self.inputs, self.outputs, self.readers = {}, {}, []
+        self.options, self.canvases, self._canary = ["tune=0"], {}, None
 
     def buf(self, C, H, W, Cs=None):
         v = V(self.arena, C, Cs or r4(C), H, W, self.N)
@@ -42,6 +49,83 @@ class Builder(object):
         v = V(0, C, Cs or r4(C), H, W, self.N, space=name)
         self.head.append("pbuf name=%s bytes=%d" % (name, self.N * H * W * v.Cs * 4))
         return v
+
+    def canvas(self, name, Cs, H, W, N=None, tail=64):
+        """a persistent buffer the host writes and reads raw (write_canvas / read_canvas) as (N, H, W, Cs) words and `tail` more behind
+        them: the operands of the op under test are sub-views of canvases (V.sub: a channel offset, Cs > C), so nothing has to be
+        imported or exported.  (import_nchw zero-fills all Cs channels from the view's first one on: it is meant for whole buffers.)"""
+        N = self.N if N is None else N
+        self.head.append("pbuf name=%s bytes=%d" % (name, (N * H * W * Cs + tail) * 4))
+        self.canvases[name] = (N, H, W, Cs, tail)
+        return V(0, Cs, Cs, H, W, N, space=name)
+
+    def flat(self, name, words, tail=64):
+        """a canvas without a pixel structure (NCHW images, logits, label bytes): `words` 32-bit words and the tail"""
+        return self.canvas(name, words, 1, 1, N=1, tail=tail)
+
+    def canary(self, name):
+        """what an output canvas holds before a run: a distinct non-zero bit pattern in every word"""
+        N, H, W, Cs, tail = self.canvases[name]
+        n = N * H * W * Cs + tail
+        if self._canary is None or self._canary.size < n:
+            self._canary = canary_words(n)
+        return self._canary[:n].copy()
+
+    def write_canvas(self, m, name, data=None):
+        """data: (N, H, W, Cs) values (the tail stays canary), None: canary everywhere"""
+        N, H, W, Cs, tail = self.canvases[name]
+        words = self.canary(name)
+        if data is not None:
+            d = np.ascontiguousarray(data)
+            assert d.dtype.itemsize == 4 and d.size == N * H * W * Cs, (name, d.dtype, d.shape)
+            words[:d.size] = d.reshape(-1).view(np.uint32)
+        m.write(name, words)
+
+    def read_canvas(self, m, name):
+        """the canvas as uint32 words: ((N, H, W, Cs), tail)"""
+        N, H, W, Cs, tail = self.canvases[name]
+        words = m.read(name, (N * H * W * Cs + tail,), np.uint32)
+        return words[:N * H * W * Cs].reshape(N, H, W, Cs), words[N * H * W * Cs:]
+
+    def untouched(self, name, words, tail, c0=0, C=0):
+        """every word of an output canvas outside channels [c0, c0 + roundup(C, 4)) of every pixel -- the tail included -- still holds
+        its canary"""
+        N, H, W, Cs, nt = self.canvases[name]
+        want = self.canary(name)
+        body = want[:N * H * W * Cs].reshape(N, H, W, Cs)
+        return np.array_equal(words[..., :c0], body[..., :c0]) and np.array_equal(words[..., c0 + r4(C):], body[..., c0 + r4(C):]) and \
+            np.array_equal(tail, want[N * H * W * Cs:])
+
+    # ---- one line per byte mover (csrc/misc.hip) ----
+    def warp(self, name, feat, flow, out, out2=None, bias=None):
+        self.lines.append("warp name=%s feat=%s flow=%s out=%s%s" % (name, feat.ref(), flow.ref(), out.ref(),
+                          "" if out2 is None else " out2=%s bias=%s" % (out2.ref(), bias)))
+
+    def dcn_cols(self, name, x, off, cols, k, s, p, d, dg):
+        self.lines.append("dcn_cols name=%s in=%s off=%s out=%s k=%d,%d s=%d,%d p=%d,%d d=%d,%d dg=%d" % (
+            name, x.ref(), off.ref(), cols.ref(), k, k, s, s, p, p, d, d, dg))
+
+    def pool(self, name, x, y, kind, k, s, p, bn=None, eps=2e-5, fixg=0, act=0):
+        self.lines.append("pool name=%s kind=%s k=%d,%d s=%d,%d p=%d,%d in=%s out=%s act=%d%s" % (
+            name, kind, k, k, s, s, p, p, x.ref(), y.ref(), act, "" if bn is None else " bn=%s eps=%r fixg=%d" % (bn, eps, fixg)))
+
+    def copy(self, name, src, dst):
+        self.lines.append("copy name=%s src=%s dst=%s" % (name, src.ref(), dst.ref()))
+
+    def prep_rgb(self, name, img, dst, H, W, bn=None, eps=2e-5, fixg=1):
+        self.lines.append("prep_rgb name=%s src=%s:0:3:3:%d:%d:%d dst=%s H=%d W=%d%s" % (
+            name, img, H, W, self.N, dst.ref(), H, W, "" if bn is None else " bn=%s eps=%r fixg=%d" % (bn, eps, fixg)))
+
+    def prep_flow(self, name, cur, prev, dst, H, W):
+        self.lines.append("prep_flow name=%s cur=%s:0:3:3:%d:%d:%d prev=%s:0:3:3:%d:%d:%d dst=%s H=%d W=%d" % (
+            name, cur, H, W, self.N, prev, H, W, self.N, dst.ref(), H, W))
+
+    def score_tail(self, name, left, logits, labels, ncls, wl, right=None, wr=None, cw=None, cb=None, extra=""):
+        H, W = 16 * left.H, 16 * left.W
+        self.lines.append("score_tail name=%s left=%s%s wl=%s%s H=%d W=%d ncls=%d logits=%s:0:%d:4:%d:%d:%d labels=%s:0:1:4:%d:%d:%d%s" % (
+            name, left.ref(), "" if right is None else " right=%s" % right.ref(), wl,
+            "" if right is None else " wr=%s cw=%s cb=%s" % (wr, cw, cb), H, W, ncls, logits, ncls, H, W, self.N, labels, H, W, self.N,
+            (" " + extra) if extra else ""))
 
     def out(self, name, v):
         self.head.append("pbuf name=%s bytes=%d" % (name, self.N * v.C * v.H * v.W * 4))
@@ -64,7 +148,12 @@ class Builder(object):
         self.readers.append((name, T, w, tile))
 
     def text(self):
-        return "\n".join(["option tune=0", "arena bytes=%d" % max(self.arena, 256)] + self.head + self.lines) + "\n"
+        return "\n".join(["option " + " ".join(self.options), "arena bytes=%d" % max(self.arena, 256)] + self.head + self.lines) + "\n"
+
+
+def canary_words(n):
+    """n distinct non-zero 32-bit patterns (an odd multiplier permutes the residues)"""
+    return np.arange(1, n + 1, dtype=np.uint32) * np.uint32(2654435761)
 
 
 def conv64(x, w, s=1, p=0, d=1):
