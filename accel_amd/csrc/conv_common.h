@@ -14,6 +14,9 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // stores, so image borders, ragged tiles and padded K need no branches.
 #define ACCEL_BUF_FLAGS 0x00020000   // gfx9 raw buffer, 32-bit data format
 #define OOB 0xFFFFFFFFu
+// the stem kernels store a pixel's 32 channels as four 16-byte pieces at base + 0 / 32 / 64 / 96: the base of a pixel past the edge of
+// the map is one from which all four stay out of range without wrapping (conv_stem_eligible: the output view ends below it)
+#define STEM_OOB 0xFFFFFF00u
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes)
 {

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f32_kernel(ConvParams p, int
             for (int a = 0; a < 4; ++a) {
                 const int oy = oy0 + 4 * rg + 2 * half + (a >> 1), ox = ox0 + (a & 1) * 32 + col;
                 const bool ok = oy < p.Ho && ox < p.Wo;
-                const unsigned off0 = ok ? (unsigned)((((n * p.Ho + oy) * p.Wo + ox) * p.yCs + jt * 32 + 4 * kk) * 4) : OOB;
+                const unsigned off0 = ok ? (unsigned)((((n * p.Ho + oy) * p.Wo + ox) * p.yCs + jt * 32 + 4 * kk) * 4) : STEM_OOB;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f32x2 lo = f32x2{acc[a][4 * g], acc[a][4 * g + 1]} * sc2[2 * g] + sf2[2 * g];
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f32_kernel(ConvParams p, int
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], floor_);       // ReLU (0) or nothing (-inf)
                     }
-                    buf_store4(yr, off0 | (unsigned)(32 * g), o);      // off0 is a multiple of 128 bytes, or all ones
+                    buf_store4(yr, off0 + (unsigned)(32 * g), o);      // (yCs is any multiple of 4: the output may be a slice of a wider buffer)
                     if (p.yr && ok) {      // range slot of the output (range.h)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { const unsigned b = range_abs_bits(o[e]); rmax = b > rmax ? b : rmax; }
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_f32_kernel(ConvParams p, int
 bool conv_stem_eligible(const ConvParams& p)
 {
     return !p.deconv2x && (!p.f16 || p.f16 == 3) && !p.narrow && p.kh == 7 && p.kw == 7 && p.sh == 2 && p.sw == 2 && p.dh == 1 && p.dw == 1 &&
-           p.ph == 3 && p.pw == 3 && p.Cin == 4 && p.Cout_store == 64 && !p.res && !p.y2;
+           p.ph == 3 && p.pw == 3 && p.Cin == 4 && p.Cout_store == 64 && !p.res && !p.y2 && p.y_bytes < STEM_OOB;
 }
 
 // OIHW (64, 3, 7, 7) -> wst[(s*2 + j)*64 + lane]: the value lane (col = lane & 31, kk = lane >> 5) feeds into K step

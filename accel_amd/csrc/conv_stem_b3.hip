@@ -200,7 +200,7 @@ __global__ __launch_bounds__(512, 2) void conv_stem_b3_kernel(ConvParams p, int 
             const bool ok = oy < p.Ho && ox < p.Wo;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const unsigned off0 = ok ? (unsigned)((((n * p.Ho + oy) * p.Wo + ox) * p.yCs + j * 32 + 4 * kk) * 4) : OOB;
+                const unsigned off0 = ok ? (unsigned)((((n * p.Ho + oy) * p.Wo + ox) * p.yCs + j * 32 + 4 * kk) * 4) : STEM_OOB;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 s4 = *reinterpret_cast<const f32x4*>(ssc + j * 32 + 8 * g + 4 * kk);
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(512, 2) void conv_stem_b3_kernel(ConvParams p, int 
                         o[e] = leaky ? (u > 0.f ? u : u * p.slope) : fmaxf(u, floor_);
                         if (p.yr && ok) { const unsigned b = range_abs_bits(o[e]); rmax = b > rmax ? b : rmax; }
                     }
-                    buf_store4(yr, off0 | (unsigned)(32 * g), o);      // off0 is a multiple of 128 bytes, or all ones
+                    buf_store4(yr, off0 + (unsigned)(32 * g), o);      // (yCs is any multiple of 4: the output may be a slice of a wider buffer)
                 }
             }
         }

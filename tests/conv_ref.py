@@ -1,0 +1,362 @@
+"""float64 reference of one plan `conv` line on channel sub-views, the bounds an fp32 evaluation of it has to meet, and the case table
+that test_conv_ref_cpu.py (the reference against the oracle and torch) and test_conv_views_gpu.py (every convolution kernel against
+the reference) share.  No tests in here.
+
+    v  = conv(x, w) * scale + shift (+ residual)        scale / shift as accel_hip.cpp finalize_conv folds them, in fp32
+    y  = act(v)                                         act: 0 none, 1 ReLU, 2 leaky 0.1
+    y2 = relu(y * scale2 + shift2)                      the dual output of the pre-activation trunk
+
+Bounds (u = 2^-24, K = taps x Cin, A = sum |x| |w| of the output = the same convolution of the absolute values):
+
+    |y - ref|   <= ((K + 8) u A + D) |scale| + 2 u (|shift| + |res| + |v|)
+    |y2 - ref2| <= |scale2| (bound of y) + 2 u |y2|
+
+the worst case of an fp32 sum in any order and with any split factor; D is what a split-operand form drops: bf16x3 2^-21 A (the six
+kept products, test_bf16x3_cpu.py), fp16x2 the distance of the form's exact model (h2_model.py, pixel scale from the view's maximum)
+from the convolution.  An f16-mode layer is specified on operands rounded to half (test_b3d_gpu.py).  Cases with K <= 576 meet the
+bars the suite already holds these kernels to as well: 1e-6 max|ref| (direct forms), 3e-6 max|ref| (Winograd), 1e-5 max(1, max|ref|)
+(f16 mode).  Winograd evaluations are held to the bars alone; a deep-K one (K > 576) to four times the error of an fp32 restatement of
+F(2x2, 3x3) on the same inputs (wino32 below), never less than 3e-6."""
+import functools
+import zlib
+
+import numpy as np
+
+import h2_model as H2
+from plan_helpers import bn_params, conv64, deconv64, r4
+
+U = 2.0 ** -24
+SLOPE = 0.1
+
+
+def f32(a):
+    return np.asarray(a, np.float32)
+
+
+def conv_out(n, k, s, p, d):
+    return (n + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+class Case(object):
+    """One conv line: family (who reports the error ratios together), launch geometry (None: the narrow kernels take none), the
+    view's shape (H x W: the INPUT map), the epilogue ("bias", "bn", "res", "dual" joined by +) and what ops() must report."""
+
+    def __init__(self, fam, tile, Cin=32, Cout=136, H=13, W=19, N=3, k=3, s=1, p=1, d=1, epi="", act=0, split="b3", f16=False, mode="conv",
+                 ksplit=False, narrow=None, odd=False, raises=False):
+        self.fam, self.tile, self.Cin, self.Cout, self.H, self.W, self.N = fam, tile, Cin, Cout, H, W, N
+        self.k, self.s, self.p, self.d, self.act, self.split, self.f16, self.mode = k, s, p, d, act, split, f16, mode
+        self.epi = frozenset(t for t in epi.split("+") if t)
+        assert self.epi <= {"bias", "bn", "res", "dual"}, epi
+        self.ksplit, self.narrow, self.odd, self.raises = ksplit, narrow, odd, raises
+        if mode == "deconv2x":
+            self.Ho, self.Wo, self.K = 2 * H - odd, 2 * W - odd, 4 * Cin
+        elif mode == "cols":
+            self.Ho, self.Wo, self.K = H, W, 9 * Cin
+        else:
+            self.Ho, self.Wo, self.K = conv_out(H, k, s, p, d), conv_out(W, k, s, p, d), k * k * Cin
+        self.wino = tile in (40, 41, 42, 43)
+
+    @property
+    def id(self):
+        return "%s-t%s-%s%s-n%d-%dx%d-%dx%d-%s%s-act%d-%s%s%s" % (
+            self.fam, "none" if self.tile is None else self.tile, "f16" if self.f16 else self.split, "" if self.mode == "conv" else "-" + self.mode,
+            self.N, self.Cin, self.Cout, self.H, self.W, "k%ds%dp%dd%d" % (self.k, self.s, self.p, self.d), "-odd" if self.odd else "", self.act,
+            "+".join(sorted(self.epi)) or "plain", "-splitk" if self.ksplit else "", "-refused" if self.raises else "")
+
+    @property
+    def data_key(self):
+        """cases with the same key share inputs, weights and epilogue constants (and so the float64 convolution)"""
+        return (self.mode, self.odd, self.Cin, self.Cout, self.H, self.W, self.N, self.k, self.s, self.p, self.d)
+
+
+def _case_of(key, **kw):
+    return Case("", 0, *key[2:], mode=key[0], odd=key[1], **kw)
+
+
+# ---- the case table ---------------------------------------------------------------------------------------------------------------
+# Launch geometries conv_tile_valid() accepts in the shipped build, each in at least one case that runs the canary, pad-zero, value
+# and NaN-independence assertions (86 / 87 are accepted by conv_tile_valid but retired in launch_conv_b3d: they must be refused):
+#   fp32 MFMA tiles      0-4 | 5-9 | 10-12 | 13, 15 (14 with 10-12: the pipelined 8-wavefront schedule) | 16-19 (LDS-DMA) | 31-35
+#   Winograd             40 (fp32), 41, 42, 43 (bf16x3 and fp16x2)
+#   stem                 50 (fp32), 51 (bf16x3 and fp16x2)
+#   weight-stationary    60
+#   bf16x3 / fp16x2      70-75 (conv_igemm.hip; bf16x3 under either setting), 76, 77, 79, 80, 81 (conv_b3r.hip), 78 (halo, fp16x2 only)
+#   f16 mode             76, 77, 79, 80, 81 and 82, 83, 84, 85, 88, 89 (conv_b3d.hip)
+#   no geometry          conv_narrow_kernel (pixel), conv_narrow3x3_kernel<4> and <8>; splitk_reduce_kernel behind 0, 40-43, 76 and
+#                        the deconvolution
+ALL_TILES = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 31, 32, 33, 34, 35]      # test_ops_gpu.ALL_TILES
+CLASSES = {"s0": [0, 1, 2, 3, 4], "s5": [5, 6, 7, 8, 9], "s10": [10, 11, 12, 14], "s13": [13, 15], "s16": [16, 17, 18, 19], "s31": [31, 32, 33, 34, 35]}
+ROT = [("bias", 0), ("bn", 2), ("res", 1), ("res+dual", 0)]      # bias; bn + leaky; residual + ReLU; dual behind a residual
+B3_TILES = [70, 71, 72, 73, 74, 75, 76, 77, 79, 80, 81]
+F16_TILES = [76, 77, 79, 80, 81, 82, 83, 84, 85, 88, 89]
+
+
+def _cases():
+    out = []
+    # fp32 MFMA tiles: 3x3 s1 p1 per id, then per schedule class a pad case (Cout 18), 3x3 s2 p2 d2 and 1x1 s2 (ktab with xCs != Cin);
+    # the epilogue rotates over the cases of a class.  Geometry 13 works in K steps of 64: Cin 64
+    for cls, ids in CLASSES.items():
+        shapes = [dict(tile=t) for t in ids] + [dict(tile=ids[0], Cout=18), dict(tile=ids[-1], s=2, p=2, d=2), dict(tile=ids[1], k=1, s=2, p=0)]
+        for i, kw in enumerate(shapes):
+            epi, act = ROT[i % 4]
+            out.append(Case("igemm-" + cls, Cin=64 if kw["tile"] == 13 else 32, epi=epi, act=act, **kw))
+    # bf16x3 / fp16x2 forms; Cin 40: K = 360, K_pad = 384 -- the out-of-range granules of ktab, the kernels' Cin % 32 != 0 loaders
+    for split in ("b3", "h2"):
+        for i, t in enumerate(B3_TILES):
+            epi, act = ROT[i % 4]
+            out.append(Case("split-" + split, t, epi=epi, act=act, split=split))
+            epi, act = ROT[(i + 2) % 4]
+            out.append(Case("split-" + split, t, Cin=40, epi=epi, act=act, split=split))
+        out.append(Case("split-" + split, 76, Cout=18, epi="bn", act=2, split=split))
+    # Winograd F(2x2, 3x3): even maps
+    for t, split in [(40, "b3"), (41, "b3"), (42, "b3"), (43, "b3"), (41, "h2"), (42, "h2"), (43, "h2")]:
+        for epi, act in ROT:
+            out.append(Case("wino-" + ("fp32" if t == 40 else split), t, Cout=72, H=12, W=18, epi=epi, act=act, split=split))
+        out.append(Case("wino-" + ("fp32" if t == 40 else split), t, Cout=18, H=12, W=18, epi="bn", act=2, split=split))
+    # ... split over K (conv_plan_split: at least 8 K steps -- of 8 channels for 40, of 16 for 41-43), finished by the split-K reduce
+    out.append(Case("wino-splitk", 40, Cin=64, Cout=72, H=8, W=8, N=1, epi="res+dual", ksplit=True))
+    for t in (41, 42, 43):
+        out.append(Case("wino-splitk", t, Cin=128, Cout=72, H=8, W=8, N=1, epi=ROT[t % 4][0], act=ROT[t % 4][1], ksplit=True))
+    # stem: a 3-channel NHWC view (Cs 12 at channel 4), 7x7 / 2
+    for t, split in [(50, "b3"), (51, "b3"), (51, "h2")]:
+        for epi, act in (("bias", 0), ("bn", 1)):
+            out.append(Case("stem", t, Cin=3, Cout=64, H=26, W=38, k=7, s=2, p=3, epi=epi, act=act, split=split))
+    out.append(Case("stem", 50, Cin=3, Cout=64, H=26, W=38, k=7, s=2, p=3, epi="res", raises=True))
+    out.append(Case("stem", 51, Cin=3, Cout=64, H=26, W=38, k=7, s=2, p=3, epi="res+dual", raises=True))
+    # weight-stationary 1x1
+    for Cin, Cout in ((64, 256), (128, 128)):
+        for epi, act in (("", 0), ("", 1), ("bn+res", 1)):
+            out.append(Case("ws", 60, Cin=Cin, Cout=Cout, k=1, p=0, epi=epi, act=act))
+    out.append(Case("ws", 60, Cin=64, Cout=256, k=1, p=0, act=2, raises=True))
+    out.append(Case("ws", 60, Cin=64, Cout=256, k=1, p=0, epi="res+dual", raises=True))
+    # halo (fp16x2 form only)
+    for d in (1, 2):
+        for epi, act in (("bn", 0), ("", 2)):
+            out.append(Case("halo", 78, Cin=64, Cout=18, H=12, W=18, p=d, d=d, epi=epi, act=act, split="h2"))
+    out.append(Case("halo", 78, Cin=64, Cout=18, H=12, W=18, epi="res", split="h2", raises=True))
+    # narrow kernels: bn + residual + leaky, the output the last slice of its canvas
+    out.append(Case("narrow", None, Cout=2, k=1, s=2, p=0, epi="bn+res", act=2, narrow="pixel"))
+    out.append(Case("narrow", None, Cout=3, k=1, s=2, p=0, epi="bn+res", act=2, narrow="pixel"))
+    out.append(Case("narrow", None, Cout=2, epi="bn+res", act=2, narrow="pixel"))
+    out.append(Case("narrow", None, Cout=2, H=48, W=62, epi="bn+res", act=2, narrow="strip4"))
+    out.append(Case("narrow", None, Cout=1, H=96, W=130, epi="bn+res", act=2, narrow="strip8"))
+    # split-K reduce: low resolution, deep K (Winograd needs an even map: 6x8)
+    for t, split, W in [(0, "b3", 7), (76, "b3", 7), (76, "h2", 7), (41, "b3", 8), (41, "h2", 8)]:
+        fam = "splitk-wino" if t == 41 else "splitk"
+        for epi, act in ROT:
+            out.append(Case(fam, t, Cin=256, H=6, W=W, N=1, epi=epi, act=act, split=split, ksplit=True))
+        out.append(Case(fam, t, Cin=256, Cout=18, H=6, W=W, N=1, epi="bn", act=2, split=split, ksplit=True))
+    # deconvolution 4x4 / 2: even and odd (cropped) outputs
+    for odd in (False, True):
+        for t, split in [(0, "b3"), (76, "b3"), (76, "h2")]:
+            out.append(Case("deconv", t, Cout=18, H=6, W=9, mode="deconv2x", epi="bias", act=2, split=split, odd=odd))
+    out.append(Case("deconv", 0, Cin=64, Cout=18, H=6, W=9, mode="deconv2x", epi="bias", act=2, odd=True, ksplit=True))
+    # column GEMM (the deformable convolutions): a dense column buffer, the output a sub-view
+    for split in ("b3", "h2"):
+        out.append(Case("cols", 81, Cout=40, H=9, W=13, mode="cols", epi="bn", act=2, split=split))
+    # f16 mode on fp32 views
+    F16_EPI = [("bias", 1), ("res", 0), ("res+dual", 0)]
+    for i, t in enumerate(F16_TILES):
+        for j, kw in enumerate((dict(), dict(s=2), dict(k=1, p=0))):
+            epi, act = F16_EPI[(i + j) % 3]
+            out.append(Case("f16", t, Cout=64 if t == 88 else 136, epi=epi, act=act, f16=True, **kw))
+    out.append(Case("f16", 84, Cout=18, epi="bias", act=1, f16=True))
+    for t in (86, 87):
+        out.append(Case("f16", t, epi="bias", act=1, f16=True, raises=True))
+    return out
+
+
+CASES = _cases()
+RUN_CASES = [c for c in CASES if not c.raises]
+REFUSED = [c for c in CASES if c.raises]
+
+
+# ---- operands ---------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _operands(key):
+    mode, odd, Cin, Cout, H, W, N, k, s, p, d = key
+    c = _case_of(key)
+    rng = np.random.default_rng(zlib.crc32(repr(key).encode()))
+    o = {}
+    if mode == "cols":
+        o["x"] = f32(rng.standard_normal((N, 9 * Cin, H, W)))          # the column buffer [pixel][tap][c] as NCHW planes
+        o["w"] = f32(rng.standard_normal((Cout, Cin, 3, 3)) / np.sqrt(c.K))
+    elif mode == "deconv2x":
+        o["x"] = f32(rng.standard_normal((N, Cin, H, W)))
+        o["w"] = f32(rng.standard_normal((Cin, Cout, 4, 4)) / np.sqrt(c.K))
+    else:
+        o["x"] = f32(rng.standard_normal((N, Cin, H, W)))
+        o["w"] = f32(rng.standard_normal((Cout, Cin, k, k)) / np.sqrt(c.K))
+    o["res"] = f32(rng.standard_normal((N, Cout, c.Ho, c.Wo)))
+    o["bias"] = f32(rng.standard_normal(Cout) * 0.5)
+    o["bn"] = bn_params(rng, "bn", Cout, Cout - 1)
+    o["bn2"] = bn_params(rng, "bn2", Cout, Cout - 1, negative=True)
+    for a in o.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return o
+
+
+def operands(case):
+    """{"x": (N, Cin, H, W) values of the input view, "w", "res", "bias", "bn", "bn2"}: shared and read-only"""
+    return _operands(case.data_key)
+
+
+def bn_fold32(bn, name, eps):
+    """accel_hip.cpp bn_fold, in fp32"""
+    g, b, mu, var = (bn[name + s] for s in ("_gamma", "_beta", "_moving_mean", "_moving_var"))
+    sd = np.sqrt(var + np.float32(eps), dtype=np.float32)
+    return g / sd, b - (g * mu) / sd
+
+
+def epilogue_constants(case, o):
+    """(scale, shift, scale2, shift2) as finalize_conv uploads them: fp32 (bias * scale added to shift)"""
+    scale, shift = np.ones(case.Cout, np.float32), np.zeros(case.Cout, np.float32)
+    if "bn" in case.epi:
+        scale, shift = bn_fold32(o["bn"], "bn", 1e-5)
+    if "bias" in case.epi:
+        shift = shift + o["bias"] * scale
+    s2 = b2 = None
+    if "dual" in case.epi:
+        s2, b2 = bn_fold32(o["bn2"], "bn2", 1e-5)
+    return f32(scale), f32(shift), s2, b2
+
+
+def plain_conv(case, x, w):
+    """the float64 contraction of a case on any operands (linear in both; nothing is rounded)"""
+    if case.mode == "deconv2x":
+        return deconv64(x, w)[:, :, :case.Ho, :case.Wo]
+    if case.mode == "cols":
+        return conv64(x, np.transpose(w, (0, 2, 3, 1)).reshape(case.Cout, 9 * case.Cin, 1, 1))
+    return conv64(x, w, case.s, case.p, case.d)
+
+
+@functools.lru_cache(maxsize=None)
+def _core(key, form):
+    """(conv, A, D): the float64 contraction, the same on absolute values, what the form `form` ("", "b3", "h2", "f16") drops"""
+    case = _case_of(key)
+    o = _operands(key)
+    x, w = o["x"].astype(np.float64), o["w"].astype(np.float64)
+    if form == "f16":
+        x, w = H2.half(x), H2.half(w)
+    conv, A = plain_conv(case, x, w), plain_conv(case, np.abs(x), np.abs(w))
+    D = np.zeros_like(A)
+    if form == "b3":
+        D = 2.0 ** -21 * A
+    elif form == "h2":
+        s = H2.range_scale(H2.float_bits(np.abs(o["x"]).max()))
+        model = H2.conv(o["x"], o["w"], s, lambda a, b: plain_conv(case, a, b), cout_axis=1 if case.mode == "deconv2x" else 0)
+        D = np.abs(model - conv)
+    return conv, A, D
+
+
+def form_of(case):
+    """which arithmetic the case's kernel runs: "" fp32 products, "b3" / "h2" split operands, "f16" half operands"""
+    if case.f16:
+        return "f16"
+    if case.tile in (41, 42, 43, 51) or (case.tile is not None and 70 <= case.tile <= 81):
+        return "b3" if case.tile in (70, 71, 72, 73, 74, 75) else case.split
+    return ""
+
+
+def act64(v, act):
+    return np.maximum(v, 0.0) if act == 1 else np.where(v > 0, v, v * np.float64(np.float32(SLOPE))) if act == 2 else v
+
+
+class Ref(object):
+    pass
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(key, form, epi, act):
+    case = _case_of(key, epi="+".join(epi), act=act)
+    o = _operands(key)
+    conv, A, D = _core(key, form)
+    scale, shift, s2, b2 = epilogue_constants(case, o)
+    bc = lambda a: a.astype(np.float64)[None, :, None, None]
+    res = o["res"].astype(np.float64) if "res" in case.epi else np.zeros_like(conv)
+    r = Ref()
+    r.A, r.K = A, case.K
+    r.v = conv * bc(scale) + bc(shift) + res
+    r.y = act64(r.v, act)
+    r.bound = ((case.K + 8) * U * A + D) * np.abs(bc(scale)) + 2 * U * (np.abs(bc(shift)) + np.abs(res) + np.abs(r.v))
+    r.y2 = r.bound2 = None
+    if s2 is not None:
+        r.y2 = np.maximum(r.y * bc(s2) + bc(b2), 0.0)
+        r.bound2 = np.abs(bc(s2)) * r.bound + 2 * U * np.abs(r.y2)
+    return r
+
+
+def reference(case):
+    """Ref of a case: v, y, y2 (None without a dual output), bound, bound2, A, K -- float64, (N, Cout, Ho, Wo); shared, do not write"""
+    return _reference(case.data_key, form_of(case), tuple(sorted(case.epi)), case.act)
+
+
+def bar(case, ref):
+    """the bar of the suite for the case's kernel at this size relative to max|ref| (None: K > 576, no bar), as a function of max|ref|"""
+    if case.wino:
+        rel = 3e-6 if case.K <= 576 else max(3e-6, 4 * wino32_error(case))
+        return lambda m: rel * m
+    if case.K > 576:
+        return None
+    if case.f16:
+        return lambda m: 1e-5 * max(1.0, m)
+    return lambda m: 1e-6 * m
+
+
+def check(case, got, got2, what=""):
+    """Hold y (and y2) -- (N, Cout, Ho, Wo) -- to the case's bound and bar; returns the largest error-to-bound ratio (Winograd: to bar)"""
+    ref = reference(case)
+    worst = 0.0
+    for name, g, want, bound in (("y", got, ref.y, ref.bound), ("y2", got2, ref.y2, ref.bound2)):
+        if want is None:
+            continue
+        assert g.shape == want.shape, (case.id, name, g.shape, want.shape)
+        assert np.isfinite(g).all(), (case.id, name, "not finite")
+        err = np.abs(g.astype(np.float64) - want)
+        b = bar(case, ref)
+        m = float(np.abs(want).max())
+        if b is not None:
+            ratio_bar = float(err.max()) / b(m)
+            if case.wino:
+                worst = max(worst, ratio_bar)
+            assert ratio_bar <= 1.0, "%s %s%s: max error %.3g above the bar %.3g" % (case.id, name, what, err.max(), b(m))
+        if not case.wino:
+            ratio = err / bound
+            worst = max(worst, float(ratio.max()))
+            at = np.unravel_index(np.argmax(ratio), ratio.shape)
+            assert ratio.max() <= 1.0, "%s %s%s: error %.3g at %s is %.3f of its bound" % (case.id, name, what, err[at], at, ratio.max())
+    return worst
+
+
+# ---- Winograd F(2x2, 3x3) in fp32 ---------------------------------------------------------------------------------------------------
+def wino32(x, w):
+    """fp32 restatement of the Winograd kernels: U = G g G^T in double rounded once to fp32 (conv_wino_pack), V = B^T d B, the products
+    summed over the channels and Y = A^T m A in fp32.  x (N, C, H, W) with even H, W (pad 1), w (K, C, 3, 3) -> (N, K, H, W) fp32"""
+    G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]])
+    Bt = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float32)
+    At = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float32)
+    N, C, H, W = x.shape
+    Uw = np.einsum('ia,kcab,jb->kcij', G, w.astype(np.float64), G).astype(np.float32)
+    xp = np.zeros((N, C, H + 2, W + 2), np.float32); xp[:, :, 1:-1, 1:-1] = x
+    d = np.stack([np.stack([xp[:, :, i:i + H:2, j:j + W:2] for j in range(4)], -1) for i in range(4)], -2)      # (N, C, H/2, W/2, 4, 4)
+    V = np.einsum('ia,nctuab->nctuib', Bt, d)
+    V = np.einsum('nctuib,jb->nctuij', V, Bt)
+    M = np.zeros((N, w.shape[0], H // 2, W // 2, 4, 4), np.float32)
+    for c in range(C):      # channel by channel: every product and every sum rounded to fp32
+        M += Uw[None, :, c, None, None] * V[:, None, c]
+    Y = np.einsum('ia,nktuab->nktuib', At, M)
+    Y = np.einsum('nktuib,jb->nktuij', Y, At)
+    return np.ascontiguousarray(Y.transpose(0, 1, 2, 4, 3, 5)).reshape(N, w.shape[0], H, W)
+
+
+@functools.lru_cache(maxsize=None)
+def _wino32_error(key):
+    o = _operands(key)
+    conv = _core(key, "")[0]
+    return float(np.abs(wino32(o["x"], o["w"]) - conv).max() / np.abs(conv).max())
+
+
+def wino32_error(case):
+    """largest error of wino32 on the case's inputs, relative to the largest |output|"""
+    return _wino32_error(case.data_key)

@@ -1,6 +1,6 @@
 """Hand-written plans for the operator tests: NHWC views of the arena, a builder of plan text (import_nchw -> convolutions -> export_nchw
 with every launch geometry forced; or the byte movers of csrc/misc.hip between sub-views of canvases the host writes and reads raw)
-and a float64 convolution.  No tests in here."""
+a float64 convolution and deconvolution, and the BatchNorm constants of the convolution tests.  No tests in here."""
 import numpy as np
 
 al = lambda b: (b + 255) // 256 * 256
@@ -168,3 +168,23 @@ def conv64(x, w, s=1, p=0, d=1):
             out += np.einsum('kc,nchw->nkhw', w[:, :, ky, kx].astype(np.float64),
                              xp[:, :, ky * d:ky * d + s * (Ho - 1) + 1:s, kx * d:kx * d + s * (Wo - 1) + 1:s])
     return out
+
+
+def deconv64(x, w):
+    """float64 Deconvolution 4x4 / stride 2 / pad 1 (NCHW, weights (Cin, Cout, 4, 4)): the full 2h x 2w output; the skip tensor's
+    Crop keeps its first rows and columns"""
+    N, C, h, w_ = x.shape
+    out = np.zeros((N, w.shape[1], 2 * h + 2, 2 * w_ + 2))
+    for ky in range(4):
+        for kx in range(4):
+            out[:, :, ky:ky + 2 * h:2, kx:kx + 2 * w_:2] += np.einsum('ck,nchw->nkhw', w[:, :, ky, kx].astype(np.float64), x)
+    return out[:, :, 1:1 + 2 * h, 1:1 + 2 * w_]
+
+
+def bn_params(rng, name, C, tc, negative=False):
+    """BatchNorm constants of mixed sign (scale and shift), small shifts; channel tc's scale is +-1 (negative: -1)"""
+    g = rng.uniform(0.5, 1.5, C) * np.where(rng.random(C) < 0.5, -1.0, 1.0)
+    g[tc] = -1.0 if negative else 1.0
+    return {name + "_gamma": g.astype(np.float32), name + "_beta": (rng.standard_normal(C) * 2.0 ** -24).astype(np.float32),
+            name + "_moving_mean": (rng.standard_normal(C) * 2.0 ** -24).astype(np.float32),
+            name + "_moving_var": np.full(C, 1.0 - 1e-5, np.float32)}

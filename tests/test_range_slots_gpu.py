@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from accel_amd import runtime
-from plan_helpers import Builder, V, al, bits, conv64, r4  # noqa: F401
+from plan_helpers import Builder, V, al, bits, bn_params, conv64, deconv64, r4  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -95,15 +95,6 @@ def planted(rng, shape, scale, at=None, sign=1.0, pattern=None):
         n, y, xx = at
         x[n, :, y, xx] = sign * BIG * scale * (pattern if pattern is not None else 1.0)
     return x.astype(np.float32)
-
-
-def bn_params(rng, name, C, tc, negative=False):
-    """BatchNorm constants of mixed sign (scale and shift), small shifts; channel tc's scale is +-1 (negative: -1)"""
-    g = rng.uniform(0.5, 1.5, C) * np.where(rng.random(C) < 0.5, -1.0, 1.0)
-    g[tc] = -1.0 if negative else 1.0
-    return {name + "_gamma": g.astype(np.float32), name + "_beta": (rng.standard_normal(C) * 2.0 ** -24).astype(np.float32),
-            name + "_moving_mean": (rng.standard_normal(C) * 2.0 ** -24).astype(np.float32),
-            name + "_moving_var": np.full(C, 1.0 - 1e-5, np.float32)}
 
 
 # ---- convolution writers: (tile, N, Cin, Cout, H, W, k, s, p, d, act, epilogue, split[, options]) --------------------------------
@@ -244,11 +235,7 @@ def test_deconv2x_epilogue_raises_the_slot(ctx, monkeypatch, odd):
     feeds.append(feeds[0])
 
     def full64(xx):
-        out = np.zeros((N, Cout, 2 * h + 2, 2 * w_ + 2))
-        for ky in range(4):
-            for kx in range(4):
-                out[:, :, ky:ky + 2 * h:2, kx:kx + 2 * w_:2] += np.einsum('ck,nchw->nkhw', b.params["w_w"][:, :, ky, kx].astype(np.float64), xx)
-        return out[:, :, 1:1 + 2 * h, 1:1 + 2 * w_] + b.params["bias"][None, :, None, None]
+        return deconv64(xx, b.params["w_w"]) + b.params["bias"][None, :, None, None]
     inner = (0, 2 * 1 + tap - 1, 2 * 2 + tap - 1)
     locate = lambda run, name: {1: (0, tc) + inner[1:], 2: (N - 1, tc) + o_last[1:]}.get(run)
     upper = None
