@@ -16,14 +16,21 @@ kept products, test_bf16x3_cpu.py), fp16x2 the distance of the form's exact mode
 from the convolution.  An f16-mode layer is specified on operands rounded to half (test_b3d_gpu.py).  Cases with K <= 576 meet the
 bars the suite already holds these kernels to as well: 1e-6 max|ref| (direct forms), 3e-6 max|ref| (Winograd), 1e-5 max(1, max|ref|)
 (f16 mode).  Winograd evaluations are held to the bars alone; a deep-K one (K > 576) to four times the error of an fp32 restatement of
-F(2x2, 3x3) on the same inputs (wino32 below), never less than 3e-6."""
+F(2x2, 3x3) on the same inputs (wino32 below), never less than 3e-6.
+
+Kernel size, stride, padding and dilation of a case are each an int or an (h, w) pair.  Beside CASES (224 lines: 217 run, 7 refused)
+the geometry sweep crosses the 26 shapes of GEOMETRY with the 22 rows of GEOMETRY_KERNELS: 572 pairs, of which 507 run, 50 must be
+refused (RULES: a K step of 64, the DMA ring's Cin % 32, conv_b3d's Cin % 16) and 15 are f16-mode requests the layer declines (padded
+Cin % 8: it stays fp32, GEOMETRY_DEMOTED) -- 11 % not run.  With the narrow kernel on the 11 anisotropic shapes, the split-K reduce on
+one deep anisotropic K and the refusals of the kernels that demand square geometry: GEOMETRY_RUN 524, GEOMETRY_REFUSED 57."""
+import collections
 import functools
 import zlib
 
 import numpy as np
 
 import h2_model as H2
-from plan_helpers import bn_params, conv64, deconv64, r4
+from plan_helpers import bn_params, conv64, deconv64, pair, r4
 
 U = 2.0 ** -24
 SLOPE = 0.1
@@ -34,33 +41,46 @@ def f32(a):
 
 
 def conv_out(n, k, s, p, d):
-    return (n + 2 * p - d * (k - 1) - 1) // s + 1
+    """output size along one axis (n an int), or (Ho, Wo) of an (H, W) map with k, s, p, d each an int or an (h, w) pair"""
+    if np.ndim(n) == 0:
+        return (n + 2 * p - d * (k - 1) - 1) // s + 1
+    return tuple(conv_out(n[i], pair(k)[i], pair(s)[i], pair(p)[i], pair(d)[i]) for i in (0, 1))
+
+
+def _g(v):
+    return "%d" % v if np.ndim(v) == 0 else "%dx%d" % tuple(v)
 
 
 class Case(object):
-    """One conv line: family (who reports the error ratios together), launch geometry (None: the narrow kernels take none), the
-    view's shape (H x W: the INPUT map), the epilogue ("bias", "bn", "res", "dual" joined by +) and what ops() must report."""
+    """One conv line: family (who reports the error ratios together), launch geometry (None: the narrow kernels take none; with
+    auto=True: no tile= at all, the heuristic chooses), the view's shape (H x W: the INPUT map), kernel size / stride / padding /
+    dilation (each an int or an (h, w) pair), the epilogue ("bias", "bn", "res", "dual" joined by +) and what ops() must report."""
 
     def __init__(self, fam, tile, Cin=32, Cout=136, H=13, W=19, N=3, k=3, s=1, p=1, d=1, epi="", act=0, split="b3", f16=False, mode="conv",
-                 ksplit=False, narrow=None, odd=False, raises=False):
+                 ksplit=False, narrow=None, odd=False, raises=False, auto=False):
         self.fam, self.tile, self.Cin, self.Cout, self.H, self.W, self.N = fam, tile, Cin, Cout, H, W, N
+        k, s, p, d = (v if np.ndim(v) == 0 else tuple(int(e) for e in v) for v in (k, s, p, d))      # hashable: part of data_key
         self.k, self.s, self.p, self.d, self.act, self.split, self.f16, self.mode = k, s, p, d, act, split, f16, mode
         self.epi = frozenset(t for t in epi.split("+") if t)
         assert self.epi <= {"bias", "bn", "res", "dual"}, epi
-        self.ksplit, self.narrow, self.odd, self.raises = ksplit, narrow, odd, raises
+        self.ksplit, self.narrow, self.odd, self.raises, self.auto = ksplit, narrow, odd, raises, auto
+        assert not auto or (tile is None and not narrow)
+        (self.kh, self.kw), (self.sh, self.sw), (self.ph, self.pw), (self.dh, self.dw) = pair(k), pair(s), pair(p), pair(d)
         if mode == "deconv2x":
             self.Ho, self.Wo, self.K = 2 * H - odd, 2 * W - odd, 4 * Cin
         elif mode == "cols":
             self.Ho, self.Wo, self.K = H, W, 9 * Cin
         else:
-            self.Ho, self.Wo, self.K = conv_out(H, k, s, p, d), conv_out(W, k, s, p, d), k * k * Cin
+            self.Ho, self.Wo = conv_out((H, W), k, s, p, d)
+            self.K = self.kh * self.kw * Cin
         self.wino = tile in (40, 41, 42, 43)
 
     @property
     def id(self):
         return "%s-t%s-%s%s-n%d-%dx%d-%dx%d-%s%s-act%d-%s%s%s" % (
-            self.fam, "none" if self.tile is None else self.tile, "f16" if self.f16 else self.split, "" if self.mode == "conv" else "-" + self.mode,
-            self.N, self.Cin, self.Cout, self.H, self.W, "k%ds%dp%dd%d" % (self.k, self.s, self.p, self.d), "-odd" if self.odd else "", self.act,
+            self.fam, "auto" if self.auto else "none" if self.tile is None else self.tile, "f16" if self.f16 else self.split,
+            "" if self.mode == "conv" else "-" + self.mode, self.N, self.Cin, self.Cout, self.H, self.W,
+            "k%ss%sp%sd%s" % (_g(self.k), _g(self.s), _g(self.p), _g(self.d)), "-odd" if self.odd else "", self.act,
             "+".join(sorted(self.epi)) or "plain", "-splitk" if self.ksplit else "", "-refused" if self.raises else "")
 
     @property
@@ -171,6 +191,120 @@ RUN_CASES = [c for c in CASES if not c.raises]
 REFUSED = [c for c in CASES if c.raises]
 
 
+# ---- the geometry sweep -----------------------------------------------------------------------------------------------------------
+# GEOMETRY: shapes only (no kernel ids); every one exercises at least one of: a pair with unequal members (each pair once on its
+# own, once all four together on a non-square map), a geometry of the networks at small size, a map smaller than its filter, an edge
+# of the K loop (K_pad = roundup(taps x roundup(Cin, 4), 32), in steps of 32), of the pixel tile (64 / 128 / 256 pixels) or of the
+# channel tile (32 / 64 / 128 / 256 channels).  The epilogue rotates over the shapes with ROT.
+#        name            Cin Cout  H   W  N  k       s       p       d             what it is for
+_G = [
+    ("k1x3",             12,   5,  9, 11, 2, (1, 3), 1,      1,      1),         # K 36 in K_pad 64, Cin % 8 == 4, Cout 5
+    ("k3x1",             32,  40,  9, 11, 2, (3, 1), 1,      1,      1),         # three steps (the DMA ring's unequal filter)
+    ("k1x7",             36,  33,  7, 14, 2, (1, 7), 1,      1,      1),         # K 252 in 256 (8 steps), Cin % 8 == 4, Cout 33
+    ("k5x3",             40,  40, 10,  9, 2, (5, 3), 1,      1,      1),         # K 600 in 608: 19 steps
+    ("s1x2",             64, 129, 11, 13, 2, 3,      (1, 2), 1,      1),         # Cout 129; 18 steps (geometry 13 takes it)
+    ("s2x1",             32,  40, 11, 14, 2, 3,      (2, 1), 1,      1),
+    ("p0x1",             64,  40, 11, 14, 2, 3,      1,      (0, 1), 1),
+    ("p2x0",             64, 260,  9, 12, 1, 3,      1,      (2, 0), 1),         # Cout 260 (every kernel takes it)
+    ("d1x2",             20,  40, 11, 14, 2, 3,      1,      1,      (1, 2)),    # K 180 in 192, Cin % 8 == 4
+    ("d2x1",             64,  40, 11, 14, 2, 3,      1,      1,      (2, 1)),
+    ("all4",             16,  72, 11, 17, 3, (3, 5), (2, 1), (1, 3), (1, 2)),    # every pair unequal, 11 x 17 -> 6 x 15
+    ("net7x7s2",          6,  33, 13, 17, 2, 7,      2,      3,      1),         # the stem's geometry on a 6-channel view (padded to 8): 13 steps
+    ("net5x5s2",         32,  40, 13, 17, 1, 5,      2,      2,      1),         # K 800: 25 steps; M 63: below every tile
+    ("net3x3s2odd",      32,  40, 13, 19, 2, 3,      2,      1,      1),
+    ("net3x3s2even",     16,  40, 12, 16, 2, 3,      2,      1,      1),
+    ("net1x1s2",         64,  40, 13, 19, 3, 1,      2,      0,      1),         # two steps
+    ("net3x3d2",         32,  40,  9, 19, 3, 3,      1,      2,      2),         # M 513 = 4 x 128 + 1, tiles straddle the three images
+    ("net3x3p0",         32,  40, 10, 18, 2, 3,      1,      0,      1),         # Ho != H; M exactly 256
+    ("map1x1",           64,  40,  1,  1, 3, 3,      1,      1,      1),         # maps smaller than the filter
+    ("map2x3",           16,   5,  2,  3, 3, 3,      1,      1,      1),
+    ("map1xW",           32,  40,  1, 19, 2, 3,      1,      1,      1),
+    ("map4x5k7",          8,  40,  4,  5, 3, 7,      2,      3,      1),
+    ("k1step",           32, 129,  8, 16, 1, 1,      1,      0,      1),         # one K step; M exactly 128
+    ("k1cin4",            4,  40,  8, 16, 2, 1,      1,      0,      1),         # K 4 in K_pad 32
+    ("k3x3cin4",          4, 260,  5,  7, 1, 3,      1,      1,      1),         # K 36 in K_pad 64
+    ("k3steps",          96,  40,  8, 16, 3, 1,      1,      0,      1),         # an odd number of steps at Cin 96; M 384
+]
+GEOMETRY = collections.OrderedDict((g[0], dict(zip(("Cin", "Cout", "H", "W", "N", "k", "s", "p", "d"), g[1:]))) for g in _G)
+ANISOTROPIC = ["k1x3", "k3x1", "k1x7", "k5x3", "s1x2", "s2x1", "p0x1", "p2x0", "d1x2", "d2x1", "all4"]
+# the sides on which NO tap of any output pixel falls outside the map (nothing there for a loader to get wrong): no padding on that
+# axis, or a strided window that ends inside an even map; every other shape has out-of-range taps on all four sides
+EDGE_FREE = {"p0x1": "tb", "p2x0": "lr", "net3x3s2even": "br", "net1x1s2": "tblr", "net3x3p0": "tblr", "k1step": "tblr", "k1cin4": "tblr",
+             "k3steps": "tblr"}
+
+
+def k_pad(case):
+    """accel_hip.cpp finalize_conv: K_pad = roundup(kh kw roundup(Cin, 4), 32)"""
+    return (case.kh * case.kw * r4(case.Cin) + 31) // 32 * 32
+
+
+# What a kernel's launcher rules out, restated once each as a predicate on the case:
+RULES = {
+    None: lambda c: True,
+    # conv_igemm.hip launch_conv_igemm: `if (p.K_pad % conv_tile_bk(tile)) return hipErrorInvalidValue;` -- geometry 13 steps K by 64
+    "bk64": lambda c: k_pad(c) % 64 == 0,
+    # conv_igemm.hip launch_conv_igemm: `if (p.Cin % 32) return hipErrorInvalidValue;   // DMA variants need wave-uniform taps per K step`
+    "dma": lambda c: r4(c.Cin) % 32 == 0,
+    # accel_hip.cpp finalize_conv: `c.f16 = (want_f16 && c.Cin % (want_f16 == 2 ? 4 : 8) == 0 && cout_store > 4) ? want_f16 : 0;` -- the layer
+    # is then an fp32 layer (ops() reports mode 0 or 3, never 1): nothing is refused, the fp32 rows already run that pair (DEMOTED)
+    "f16": lambda c: r4(c.Cin) % 8 == 0,
+    # conv_b3d.hip `bool conv_b3d_eligible(const ConvParams& p) { return p.Cin % 16 == 0 && p.ktab != nullptr; }`, and launch_conv_igemm's
+    # `if (!p.wb3r || p.f16 != 1) return hipErrorInvalidValue;` for the layers the rule above made fp32
+    "b3d": lambda c: r4(c.Cin) % 16 == 0,
+}
+# one launch geometry per kernel template and loader path: (family, id, ACCEL_SPLIT, f16 mode, rule)
+GEOMETRY_KERNELS = [
+    ("geo-igemm", 0, "b3", False, None), ("geo-igemm", 5, "b3", False, None), ("geo-igemm", 10, "b3", False, None),
+    ("geo-igemm", 13, "b3", False, "bk64"), ("geo-igemm", 31, "b3", False, None), ("geo-igemm", 16, "b3", False, "dma"),
+    ("geo-b3", 70, "b3", False, None), ("geo-b3", 75, "b3", False, None),
+    ("geo-b3r-b3", 76, "b3", False, None), ("geo-b3r-b3", 77, "b3", False, None), ("geo-b3r-b3", 80, "b3", False, None),
+    ("geo-b3r-h2", 76, "h2", False, None), ("geo-b3r-h2", 77, "h2", False, None), ("geo-b3r-h2", 80, "h2", False, None),
+    ("geo-f16", 0, "b3", True, "f16"), ("geo-f16", 10, "b3", True, "f16"), ("geo-f16-b3r", 76, "b3", True, "f16"),
+    ("geo-f16-b3d", 82, "b3", True, "b3d"), ("geo-f16-b3d", 84, "b3", True, "b3d"), ("geo-f16-b3d", 88, "b3", True, "b3d"),
+    # no tile= at all: conv_pick_tile chooses (and conv_plan_split splits K where it likes)
+    ("geo-auto", None, "b3", False, None), ("geo-auto", None, "h2", False, None),
+]
+# the ids conv_tile_valid() accepts (conv_igemm.hip)
+VALID_TILES = set(range(0, 20)) | set(range(31, 36)) | {40, 41, 42, 43, 50, 51, 60, 78} | set(range(70, 78)) | {79, 80, 81} | set(range(82, 90))
+
+
+def _geometry_cases():
+    run, refused, demoted = [], [], []
+    for i, (name, g) in enumerate(GEOMETRY.items()):
+        epi, act = ROT[i % 4]
+        for fam, tile, split, f16, rule in GEOMETRY_KERNELS:
+            c = Case(fam, tile, epi=epi, act=act, split=split, f16=f16, auto=tile is None, **g)
+            if RULES[rule](c):
+                run.append(c)
+            elif rule == "f16":
+                demoted.append(c)
+            else:
+                c.raises = True
+                refused.append(c)
+    # the narrow pixel kernel (no geometry id) on the anisotropic shapes, Cout 2 and 3 in turn; it has no second output
+    for i, name in enumerate(ANISOTROPIC):
+        epi, act = [("bias", 0), ("bn+res", 2), ("res", 1)][i % 3]
+        run.append(Case("geo-narrow", None, epi=epi, act=act, narrow="pixel", **dict(GEOMETRY[name], Cout=2 + i % 2)))
+    # ... and the split forms are not offered to narrow outputs (accel_hip.cpp finalize_conv: "the bf16x3 kernel takes layers with
+    # more than 4 output channels only")
+    for t, split in ((70, "b3"), (76, "b3"), (76, "h2")):
+        refused.append(Case("geo-narrow", t, epi="bias", split=split, raises=True, **dict(GEOMETRY["k1x3"], Cout=3)))
+    # the split-K reduce behind 0 and behind 76 on one deep-K shape with every pair unequal: 6 x 9 -> 3 x 7, K 768 in 24 steps
+    deep = dict(Cin=256, Cout=136, H=6, W=9, N=1, k=(1, 3), s=(2, 1), p=(0, 1), d=(1, 2))
+    for t, split in ((0, "b3"), (76, "b3"), (76, "h2")):
+        for epi, act in (ROT[3], ROT[1]):
+            run.append(Case("geo-splitk", t, epi=epi, act=act, split=split, ksplit=True, **deep))
+    # kernels that demand square geometry in their *_eligible functions: Winograd, stem, halo, weight-stationary
+    refused.append(Case("geo-square", 40, Cout=72, H=12, W=18, k=(3, 1), p=(1, 0), epi="bias", raises=True))
+    refused.append(Case("geo-square", 50, Cin=3, Cout=64, H=26, W=38, k=7, s=(1, 2), p=3, epi="bias", raises=True))
+    refused.append(Case("geo-square", 78, Cin=64, Cout=18, H=12, W=18, s=(1, 2), epi="bn", split="h2", raises=True))
+    refused.append(Case("geo-square", 60, Cin=64, Cout=256, k=1, p=0, s=(1, 2), raises=True))
+    return run, refused, demoted
+
+
+GEOMETRY_RUN, GEOMETRY_REFUSED, GEOMETRY_DEMOTED = _geometry_cases()
+
+
 # ---- operands ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _operands(key):
@@ -186,7 +320,7 @@ def _operands(key):
         o["w"] = f32(rng.standard_normal((Cin, Cout, 4, 4)) / np.sqrt(c.K))
     else:
         o["x"] = f32(rng.standard_normal((N, Cin, H, W)))
-        o["w"] = f32(rng.standard_normal((Cout, Cin, k, k)) / np.sqrt(c.K))
+        o["w"] = f32(rng.standard_normal((Cout, Cin, c.kh, c.kw)) / np.sqrt(c.K))
     o["res"] = f32(rng.standard_normal((N, Cout, c.Ho, c.Wo)))
     o["bias"] = f32(rng.standard_normal(Cout) * 0.5)
     o["bn"] = bn_params(rng, "bn", Cout, Cout - 1)
@@ -263,6 +397,15 @@ def act64(v, act):
     return np.maximum(v, 0.0) if act == 1 else np.where(v > 0, v, v * np.float64(np.float32(SLOPE))) if act == 2 else v
 
 
+def finish64(case, conv):
+    """y of a case in float64 from ANY contraction `conv` (N, Cout, Ho, Wo): scale, shift, residual and activation of the case"""
+    o = operands(case)
+    scale, shift, _, _ = epilogue_constants(case, o)
+    bc = lambda a: a.astype(np.float64)[None, :, None, None]
+    res = o["res"].astype(np.float64) if "res" in case.epi else 0.0
+    return act64(conv * bc(scale) + bc(shift) + res, case.act)
+
+
 class Ref(object):
     pass
 
@@ -278,7 +421,7 @@ def _reference(key, form, epi, act):
     r = Ref()
     r.A, r.K = A, case.K
     r.v = conv * bc(scale) + bc(shift) + res
-    r.y = act64(r.v, act)
+    r.y = finish64(case, conv)
     r.bound = ((case.K + 8) * U * A + D) * np.abs(bc(scale)) + 2 * U * (np.abs(bc(shift)) + np.abs(res) + np.abs(r.v))
     r.y2 = r.bound2 = None
     if s2 is not None:

@@ -4,6 +4,8 @@
 also returns S, the same expression evaluated on |operands|.  No tests in here."""
 import numpy as np
 
+from plan_helpers import pair
+
 U = 2.0 ** -24          # unit roundoff of fp32
 
 # what a dcn_cols tap did (bit flags of the branch record)
@@ -59,21 +61,22 @@ def conv_out(n, k, s, p, d):
 
 
 def dcn_cols64(x, off, k, s, p, d, dg, grp=None):
-    """DCN-v1 sampling (misc.hip dcn_cols_body): x (N, H, W, C), off (N, Ho, Wo, dg * 2 * k * k) with (dy, dx) of tap t of group g at
-    channels g * 2 k k + 2 t; a tap is zero unless 0 <= h_im < H and 0 <= w_im < W; floor(h) >= height - 1 (relative to the window's
-    first row) clamps both rows to the last one and drops the fraction, likewise in w.  grp: deformable group of every channel of x
-    (default: C / dg consecutive channels per group).  Returns col (N, Ho, Wo, k * k, C), S, and the branch record
-    (N, Ho, Wo, dg, k * k) of flags above."""
+    """DCN-v1 sampling (misc.hip dcn_cols_body): x (N, H, W, C), off (N, Ho, Wo, dg * 2 * taps) with (dy, dx) of tap t = i kw + j of
+    group g at channels g * 2 taps + 2 t; k, s, p, d each an int or an (h, w) pair; a tap is zero unless 0 <= h_im < H and
+    0 <= w_im < W; floor(h) >= height - 1 (relative to the window's first row) clamps both rows to the last one and drops the fraction,
+    likewise in w.  grp: deformable group of every channel of x (default: C / dg consecutive channels per group).  Returns col
+    (N, Ho, Wo, taps, C), S, and the branch record (N, Ho, Wo, dg, taps) of flags above."""
     x, off = f64(x), f64(off)
     N, H, W, C = x.shape
-    taps = k * k
-    Ho, Wo = conv_out(H, k, s, p, d), conv_out(W, k, s, p, d)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = pair(k), pair(s), pair(p), pair(d)
+    taps = kh * kw
+    Ho, Wo = conv_out(H, kh, sh, ph, dh), conv_out(W, kw, sw, pw, dw)
     grp = np.arange(C) // (C // dg) if grp is None else np.asarray(grp)
     off = off.reshape(N, Ho, Wo, dg, taps, 2)
     oh, ow = off[..., 0], off[..., 1]
-    i, j = (np.arange(taps) // k).reshape(1, 1, 1, 1, taps), (np.arange(taps) % k).reshape(1, 1, 1, 1, taps)
-    h_in, w_in = (np.arange(Ho) * s - p).reshape(1, Ho, 1, 1, 1), (np.arange(Wo) * s - p).reshape(1, 1, Wo, 1, 1)
-    h_im, w_im = h_in + i * d + oh, w_in + j * d + ow
+    i, j = (np.arange(taps) // kw).reshape(1, 1, 1, 1, taps), (np.arange(taps) % kw).reshape(1, 1, 1, 1, taps)
+    h_in, w_in = (np.arange(Ho) * sh - ph).reshape(1, Ho, 1, 1, 1), (np.arange(Wo) * sw - pw).reshape(1, 1, Wo, 1, 1)
+    h_im, w_im = h_in + i * dh + oh, w_in + j * dw + ow
     inside = (h_im >= 0) & (w_im >= 0) & (h_im < H) & (w_im < W)
 
     def axis(rel, size):           # rel: coordinate relative to the window start, size: rows (columns) from there to the border
@@ -84,8 +87,8 @@ def dcn_cols64(x, off, k, s, p, d, dg, grp=None):
         high = np.where(cl, low, low + 1)
         return low.astype(np.int64), high.astype(np.int64), rel - low, cl
 
-    h_low, h_high, lh, ch = axis(i * d + oh, H - h_in)
-    w_low, w_high, lw, cw = axis(j * d + ow, W - w_in)
+    h_low, h_high, lh, ch = axis(i * dh + oh, H - h_in)
+    w_low, w_high, lw, cw = axis(j * dw + ow, W - w_in)
     hh, hw = 1 - lh, 1 - lw
     y0, y1 = np.clip(h_in + h_low, 0, H - 1), np.clip(h_in + h_high, 0, H - 1)
     x0, x1 = np.clip(w_in + w_low, 0, W - 1), np.clip(w_in + w_high, 0, W - 1)
@@ -116,15 +119,17 @@ def pool_out(n, k, s, p, full):
 
 
 def pool64(x, kind, k, s, p, full):
-    """mx.symbol.Pooling on (N, H, W, C): max ignores the padding; avg divides by the window's area clipped to [-p, size + p)"""
+    """mx.symbol.Pooling on (N, H, W, C): max ignores the padding; avg divides by the window's area clipped to [-p, size + p);
+    k, s, p each an int or an (h, w) pair"""
     x = f64(x)
     N, H, W, C = x.shape
-    Ho, Wo = pool_out(H, k, s, p, full), pool_out(W, k, s, p, full)
+    (kh, kw), (sh, sw), (ph, pw) = pair(k), pair(s), pair(p)
+    Ho, Wo = pool_out(H, kh, sh, ph, full), pool_out(W, kw, sw, pw, full)
     out, S = np.zeros((N, Ho, Wo, C)), np.zeros((N, Ho, Wo, C))
     for oy in range(Ho):
         for ox in range(Wo):
-            hs, ws = oy * s - p, ox * s - p
-            he, we = min(hs + k, H + p), min(ws + k, W + p)
+            hs, ws = oy * sh - ph, ox * sw - pw
+            he, we = min(hs + kh, H + ph), min(ws + kw, W + pw)
             area = (he - hs) * (we - ws)
             win = x[:, max(hs, 0):min(he, H), max(ws, 0):min(we, W)].reshape(N, -1, C)
             if kind == "max":
@@ -292,11 +297,33 @@ def dcn_offsets(rng, shape):
 
 def dcn_inputs(case, N=3, gaussian=False):
     k, s, p, d, dg, C, H, W, seed = case
-    rng = np.random.default_rng(3000 + seed + 17 * H + W + 5 * C + k + 3 * dg)
-    Ho, Wo = conv_out(H, k, s, p, d), conv_out(W, k, s, p, d)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = pair(k), pair(s), pair(p), pair(d)
+    rng = np.random.default_rng(3000 + seed + 17 * H + W + 5 * C + (k if np.ndim(k) == 0 else 100 * kh + 10 * kw) + 3 * dg)
+    Ho, Wo = conv_out(H, kh, sh, ph, dh), conv_out(W, kw, sw, pw, dw)
     x = rng.standard_normal((N, H, W, C)) if gaussian else dyadic(rng, (N, H, W, C), 0.25, -8, 8)
-    off = dcn_offsets(rng, (N, Ho, Wo, dg * 2 * k * k))
+    off = dcn_offsets(rng, (N, Ho, Wo, dg * 2 * kh * kw))
     return x.astype(np.float32), off.astype(np.float32)
+
+
+# the generic kernels on unequal pairs: (k, s, p, d, dg, C, H, W, seed), all through dcn_cols_kernel (launch_dcn_cols takes the
+# three-taps-per-thread kernel for kh == kw == 3 alone)
+DCN_PAIR_CASES = [
+    ((1, 3), 1, (0, 2), (1, 2), 1, 16, 7, 9, 0),
+    ((1, 3), 1, (0, 2), (1, 2), 2, 16, 7, 9, 0),
+    ((3, 1), 1, (0, 2), (1, 2), 1, 16, 7, 9, 0),
+    ((3, 1), 1, (0, 2), (1, 2), 2, 32, 7, 9, 0),
+]
+# (kind, k, s, p, full): through pool_kernel (launch_pool takes the nine-loads kernel for max 3x3 / 2 alone)
+# (on the 13 x 19 map both conventions keep the same windows at these strides)
+POOL_PAIR_CASES = [("max", (3, 2), (2, 1), (1, 0), False), ("max", (2, 3), (1, 2), (0, 1), False),
+                   ("avg", (3, 2), (2, 1), (1, 0), False), ("avg", (2, 3), (1, 2), (0, 1), True)]
+
+
+def pool_dyadic_inputs(C, N=3, seed=0):
+    """multiples of 1/4 in [-8, 8]: window sums are exact in fp32, and so is the division by a window of 1, 2 or 4 elements; the
+    division by 3 or 6 rounds once"""
+    H, W = POOL_HW
+    return dyadic(np.random.default_rng(4200 + seed + C), (N, H, W, C), 0.25, -8, 8).astype(np.float32)
 
 
 def branch_counts(rec):

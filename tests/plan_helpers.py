@@ -8,6 +8,11 @@ r4 = lambda c: (c + 3) // 4 * 4
 bits = lambda v: int(np.float32(v).view(np.uint32)) & 0x7FFFFFFF
 
 
+def pair(v):
+    """(h, w) of a kernel size, stride, padding or dilation given as an int (both the same) or as a pair"""
+    return (int(v),) * 2 if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
+
+
 class V(object):
     """an NHWC view of the arena: offset, channels, channel stride, H, W, images"""
 
@@ -102,12 +107,14 @@ class Builder(object):
                           "" if out2 is None else " out2=%s bias=%s" % (out2.ref(), bias)))
 
     def dcn_cols(self, name, x, off, cols, k, s, p, d, dg):
+        """k, s, p, d: an int or an (h, w) pair"""
         self.lines.append("dcn_cols name=%s in=%s off=%s out=%s k=%d,%d s=%d,%d p=%d,%d d=%d,%d dg=%d" % (
-            name, x.ref(), off.ref(), cols.ref(), k, k, s, s, p, p, d, d, dg))
+            (name, x.ref(), off.ref(), cols.ref()) + pair(k) + pair(s) + pair(p) + pair(d) + (dg,)))
 
     def pool(self, name, x, y, kind, k, s, p, bn=None, eps=2e-5, fixg=0, act=0):
+        """k, s, p: an int or an (h, w) pair"""
         self.lines.append("pool name=%s kind=%s k=%d,%d s=%d,%d p=%d,%d in=%s out=%s act=%d%s" % (
-            name, kind, k, k, s, s, p, p, x.ref(), y.ref(), act, "" if bn is None else " bn=%s eps=%r fixg=%d" % (bn, eps, fixg)))
+            (name, kind) + pair(k) + pair(s) + pair(p) + (x.ref(), y.ref(), act, "" if bn is None else " bn=%s eps=%r fixg=%d" % (bn, eps, fixg))))
 
     def copy(self, name, src, dst):
         self.lines.append("copy name=%s src=%s dst=%s" % (name, src.ref(), dst.ref()))
@@ -157,16 +164,17 @@ def canary_words(n):
 
 
 def conv64(x, w, s=1, p=0, d=1):
-    """float64 NCHW convolution, zero padding"""
+    """float64 NCHW convolution, zero padding; s, p, d: an int or an (h, w) pair"""
     N, C, H, W = x.shape
     K, _, kh, kw = w.shape
-    Ho, Wo = (H + 2 * p - d * (kh - 1) - 1) // s + 1, (W + 2 * p - d * (kw - 1) - 1) // s + 1
-    xp = np.zeros((N, C, H + 2 * p, W + 2 * p)); xp[:, :, p:p + H, p:p + W] = x
+    (sh, sw), (ph, pw), (dh, dw) = pair(s), pair(p), pair(d)
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    xp = np.zeros((N, C, H + 2 * ph, W + 2 * pw)); xp[:, :, ph:ph + H, pw:pw + W] = x
     out = np.zeros((N, K, Ho, Wo))
     for ky in range(kh):
         for kx in range(kw):
             out += np.einsum('kc,nchw->nkhw', w[:, :, ky, kx].astype(np.float64),
-                             xp[:, :, ky * d:ky * d + s * (Ho - 1) + 1:s, kx * d:kx * d + s * (Wo - 1) + 1:s])
+                             xp[:, :, ky * dh:ky * dh + sh * (Ho - 1) + 1:sh, kx * dw:kx * dw + sw * (Wo - 1) + 1:sw])
     return out
 
 

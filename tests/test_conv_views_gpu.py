@@ -21,7 +21,18 @@ Every test prints its largest error-to-bound ratio (Winograd: error to bar; run 
 family.  One run on an MI355X: igemm 0-4 / 5-9 / 31-35 0.100, 10-12 + 14 0.078, 13 / 15 0.083, 16-19 0.078; bf16x3 and fp16x2 forms
 0.014; Winograd fp32 0.077, bf16x3 0.066, fp16x2 0.073, split over K 0.081, behind the deep-K reduce 0.092; weight-stationary 0.065;
 halo 0.002; narrow 0.036; split-K reduce below 0.001; deconvolution 0.034; column GEMM 0.009; f16 mode 0.054 (the stem cases of that
-run failed: see conv_stem.hip's output stores).  The whole file took 3 s."""
+run failed: see conv_stem.hip's output stores).  The whole file took 3 s.
+
+The geometry sweep (test_conv_geometry_on_sub_views) runs the same six assertions on conv_ref.GEOMETRY_RUN: 26 small shapes -- kernel
+size, stride, padding and dilation with unequal height and width members (each pair on its own, and all four on a non-square map),
+the networks' geometries, maps smaller than the filter, one / two / three / odd K steps and K far below K_pad, Cin % 8 == 4, M below,
+at and one above the pixel tiles, Cout 5 / 33 / 129 / 260 -- crossed with one launch geometry per kernel template and loader path
+(fp32 MFMA 0, 5, 10, 13, 31 and the DMA ring 16; conv_igemm_b3 70, 75; conv_b3r 76, 77, 80 as bf16x3 and as fp16x2; f16 mode on
+conv_igemm_f16 0, 10, conv_b3r 76 and conv_b3d 82, 84, 88) and with no tile= at all under both split settings (the id conv_pick_tile
+reports must be part of the build), plus the narrow pixel kernel on the anisotropic shapes and the split-K reduce behind 0 and 76
+on one deep anisotropic K: 524 cases.  57 more must be refused (conv_ref.RULES and the kernels that demand square geometry), and 15
+f16-mode requests on layers with a padded Cin off a multiple of 8 must report an fp32 layer.  The sweep has not been run on an
+MI355X yet (none could be had when it was written): its ratios per family (geo-*) are printed by the last test and belong here."""
 import collections
 
 import numpy as np
@@ -30,7 +41,7 @@ import pytest
 import conv_ref as R
 import h2_model as H2
 from accel_amd import runtime
-from plan_helpers import Builder, r4
+from plan_helpers import Builder, pair, r4
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +61,7 @@ def layout(case):
     Cs = r4(case.Cout) + 12
     # a cropped deconvolution must not write the rows it drops: behind the last image they would land in the tail
     tail = 64 + ((case.Wo + 2) * Cs if case.odd else 0)
-    y = b.canvas("Y", Cs, case.Ho, case.Wo, tail=tail).sub(Cs - 4 if case.tile is None else 8, case.Cout)
+    y = b.canvas("Y", Cs, case.Ho, case.Wo, tail=tail).sub(Cs - 4 if case.narrow else 8, case.Cout)
     res = b.canvas("R", r4(case.Cout) + 8, case.Ho, case.Wo).sub(4, case.Cout) if "res" in case.epi else None
     y2 = b.canvas("Y2", r4(case.Cout) + 16, case.Ho, case.Wo).sub(12, case.Cout) if "dual" in case.epi else None
     return b, x, y, res, y2
@@ -59,12 +70,12 @@ def layout(case):
 def conv_line(case, x, y, res, y2):
     t = ["conv name=c in=%s out=%s w=c_w act=%d slope=%r cin=%d cout=%d mode=%s" % (x.ref(), y.ref(), case.act, R.SLOPE, case.Cin, case.Cout, case.mode)]
     if case.mode == "conv":
-        t.append("k=%d,%d s=%d,%d p=%d,%d d=%d,%d" % ((case.k,) * 2 + (case.s,) * 2 + (case.p,) * 2 + (case.d,) * 2))
+        t.append("k=%d,%d s=%d,%d p=%d,%d d=%d,%d" % (pair(case.k) + pair(case.s) + pair(case.p) + pair(case.d)))
     elif case.mode == "cols":
         t.append("wk=3,3")
     if case.tile is not None:
         t.append("tile=%d" % case.tile)
-    if not case.ksplit:
+    if not case.ksplit and not case.auto:
         t.append("nosplit=1")
     if "bias" in case.epi:
         t.append("bias=c_b")
@@ -119,8 +130,8 @@ def params_of(case, o):
     return p
 
 
-@pytest.mark.parametrize("case", R.RUN_CASES, ids=lambda c: c.id)
-def test_conv_on_sub_views(ctx, monkeypatch, case):
+def on_sub_views(ctx, monkeypatch, case):
+    """the six assertions of the module docstring on one case"""
     monkeypatch.setenv("ACCEL_SPLIT", case.split)
     o = R.operands(case)
     b, x, y, res, y2 = layout(case)
@@ -129,13 +140,17 @@ def test_conv_on_sub_views(ctx, monkeypatch, case):
     try:
         # ---- what runs: the forced geometry, split over K or not, the narrow kernel the shape selects (misc.hip launch_conv_narrow)
         (op,) = plan.ops()
-        assert op["narrow"] == (1 if case.tile is None else 0), op
-        if case.tile is not None:
-            assert op["tile"] == case.tile, op
-        assert (op["ksplit"] > 1) == case.ksplit, op
+        assert op["narrow"] == (1 if case.narrow else 0), op
+        if case.auto:      # no tile=: whatever conv_pick_tile chose is part of the build, split over K or not as conv_plan_split likes
+            assert op["tile"] in R.VALID_TILES and op["ksplit"] >= 1, op
+        else:
+            assert (case.tile is None) == bool(case.narrow)
+            if case.tile is not None:
+                assert op["tile"] == case.tile, op
+            assert (op["ksplit"] > 1) == case.ksplit, op
         if case.narrow:
             M = case.N * case.Ho * case.Wo
-            strip = case.k == 3 and case.s == 1 and case.d == 1 and case.p == 1 and case.Cout <= 2
+            strip = (pair(case.k), pair(case.s), pair(case.d), pair(case.p)) == ((3, 3), (1, 1), (1, 1), (1, 1)) and case.Cout <= 2
             want = "strip8" if strip and M >= 8 * 4 * 1024 else "strip4" if strip and M >= 4 * 4 * 512 else "pixel"
             assert want == case.narrow and (want == "pixel" or case.Wo % int(want[-1])), (M, case.Wo)
         form = R.form_of(case)
@@ -190,10 +205,22 @@ def test_conv_on_sub_views(ctx, monkeypatch, case):
         m.close()
 
 
-@pytest.mark.parametrize("case", R.REFUSED, ids=lambda c: c.id)
+@pytest.mark.parametrize("case", R.RUN_CASES, ids=lambda c: c.id)
+def test_conv_on_sub_views(ctx, monkeypatch, case):
+    on_sub_views(ctx, monkeypatch, case)
+
+
+@pytest.mark.parametrize("case", R.GEOMETRY_RUN, ids=lambda c: c.id)
+def test_conv_geometry_on_sub_views(ctx, monkeypatch, case):
+    """the geometry sweep (conv_ref.GEOMETRY x GEOMETRY_KERNELS): unequal height and width members of every pair, the networks'
+    geometries at small size, maps smaller than the filter, the edges of the K loop and of both tiles"""
+    on_sub_views(ctx, monkeypatch, case)
+
+
+@pytest.mark.parametrize("case", R.REFUSED + R.GEOMETRY_REFUSED, ids=lambda c: c.id)
 def test_forced_geometry_refuses_what_it_cannot_run(ctx, monkeypatch, case):
-    """an epilogue (or a retired id) the kernel's eligibility rules out is an error, not something ignored: conv_*_eligible and the
-    checks of accel_hip.cpp / launch_conv_igemm"""
+    """an epilogue, a retired id or a geometry the kernel's eligibility rules out is an error, not something ignored: conv_*_eligible
+    and the checks of accel_hip.cpp / launch_conv_igemm (conv_ref.RULES restates those of the geometry sweep)"""
     monkeypatch.setenv("ACCEL_SPLIT", case.split)
     b, x, y, res, y2 = layout(case)
     b.lines.append(conv_line(case, x, y, res, y2))
@@ -203,6 +230,21 @@ def test_forced_geometry_refuses_what_it_cannot_run(ctx, monkeypatch, case):
             plan.run()
         finally:
             m.close()
+
+
+@pytest.mark.parametrize("case", R.GEOMETRY_DEMOTED, ids=lambda c: c.id)
+def test_f16_mode_leaves_layers_it_cannot_take_in_fp32(ctx, monkeypatch, case):
+    """dtype=f16 on a layer whose padded Cin is no multiple of 8 (a K chunk of 8 would straddle two taps): the layer stays an fp32
+    layer and says so through ops() -- those pairs are the fp32 rows of the sweep, nothing is refused and nothing runs in half"""
+    monkeypatch.setenv("ACCEL_SPLIT", case.split)
+    b, x, y, res, y2 = layout(case)
+    b.lines.append(conv_line(case, x, y, res, y2))
+    m, plan = bind(ctx, case, b, params_of(case, R.operands(case)))
+    try:
+        (op,) = plan.ops()
+        assert op["mode"] == 0 and op["tile"] == case.tile, op
+    finally:
+        m.close()
 
 
 def test_zz_report_the_ratios():

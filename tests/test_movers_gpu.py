@@ -13,7 +13,7 @@ import pytest
 import movers_ref as R
 from accel_amd import runtime
 from movers_ref import U
-from plan_helpers import Builder, V, r4
+from plan_helpers import Builder, V, pair, r4
 
 pytestmark = pytest.mark.gpu
 
@@ -121,7 +121,8 @@ def test_warp_bounded(ctx, H, W, mag):
 # ---- dcn_cols ---------------------------------------------------------------------------------------------------------------------
 def dcn_plan(k, s, p, d, dg, C, H, W, N, half=False):
     b = Builder(N)
-    taps, Ho, Wo = k * k, R.conv_out(H, k, s, p, d), R.conv_out(W, k, s, p, d)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = pair(k), pair(s), pair(p), pair(d)
+    taps, Ho, Wo = kh * kw, R.conv_out(H, kh, sh, ph, dh), R.conv_out(W, kw, sw, pw, dw)
     x = b.canvas("X", C + 8, H, W).sub(4, C)
     off = b.canvas("OFF", r4(dg * 2 * taps) + 12, Ho, Wo).sub(8, dg * 2 * taps)
     if not half:
@@ -152,6 +153,23 @@ def test_dcn_cols_exact(ctx, case):
         assert n >= R.DCN_MIN_TAPS, (what, n)
     if k == 3:
         assert R.dcn_blocks(case) == R.DCN_BLOCKS[R.DCN_CASES.index(case)]
+    b, x, off, cols = dcn_plan(k, s, p, d, dg, C, H, W, 3)
+    res = run(ctx, b, {}, {"X": put(filled(3, b, "X"), x, x_v), "OFF": put(filled(4, b, "OFF"), off, off_v)}, ["COL"])
+    np.testing.assert_array_equal(view_of(b, res, "COL", cols).reshape(ref.shape), ref)
+
+
+@pytest.mark.parametrize("case", R.DCN_PAIR_CASES, ids=lambda c: "k%dx%ds%dx%dp%dx%dd%dx%ddg%d_c%d_%dx%d" % (
+    pair(c[0]) + pair(c[1]) + pair(c[2]) + pair(c[3]) + tuple(c[4:8])))
+def test_dcn_cols_exact_with_unequal_pairs(ctx, case):
+    """1x3 and 3x1 windows, dilation (1, 2), padding (0, 2), one and two deformable groups, dyadic inputs: bit for bit, every branch
+    of the rule taken.  The plan reports no kernel for a mover; launch_dcn_cols (misc.hip) takes the three-taps-per-thread kernel
+    only `if (p.kh == 3 && p.kw == 3)`, so these run dcn_cols_kernel: tap t = i kw + j, offsets at g 2 taps + 2 t."""
+    k, s, p, d, dg, C, H, W, _ = case
+    assert pair(k) != (3, 3) and pair(k)[0] != pair(k)[1] and pair(p)[0] != pair(p)[1] and pair(d)[0] != pair(d)[1]
+    x_v, off_v = R.dcn_inputs(case)
+    ref, _, rec = R.dcn_cols64(x_v, off_v, k, s, p, d, dg)
+    for what, n in R.branch_counts(rec).items():
+        assert n >= R.DCN_MIN_TAPS, (what, n)
     b, x, off, cols = dcn_plan(k, s, p, d, dg, C, H, W, 3)
     res = run(ctx, b, {}, {"X": put(filled(3, b, "X"), x, x_v), "OFF": put(filled(4, b, "OFF"), off, off_v)}, ["COL"])
     np.testing.assert_array_equal(view_of(b, res, "COL", cols).reshape(ref.shape), ref)
@@ -217,8 +235,9 @@ def test_copy_between_sub_views(ctx, C):
 def pool_plan(C, k, s, p, full, kind, bn=None, fixg=0):
     b = Builder(3)
     H, W = R.POOL_HW
+    (kh, kw), (sh, sw), (ph, pw) = pair(k), pair(s), pair(p)
     x = b.canvas("X", r4(C) + 8, H, W).sub(4, C)
-    y = b.canvas("Y", r4(C) + 12, R.pool_out(H, k, s, p, full), R.pool_out(W, k, s, p, full)).sub(8, C)
+    y = b.canvas("Y", r4(C) + 12, R.pool_out(H, kh, sh, ph, full), R.pool_out(W, kw, sw, pw, full)).sub(8, C)
     b.pool("q", x, y, kind, k, s, p, bn=bn, fixg=fixg, act=1 if bn else 0)
     return b, x, y
 
@@ -235,6 +254,28 @@ def test_max_pool_exact(ctx, kind, k, s, p, full, C):
     b, x, y = pool_plan(C, k, s, p, full, kind)
     res = run(ctx, b, {}, {"X": put(filled(6, b, "X"), x, x_v)}, ["Y"])
     np.testing.assert_array_equal(view_of(b, res, "Y", y), R.pool64(x_v, kind, k, s, p, full)[0])
+
+
+@pytest.mark.parametrize("C", R.POOL_C)
+@pytest.mark.parametrize("kind,k,s,p,full", R.POOL_PAIR_CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_pool_with_unequal_pairs(ctx, kind, k, s, p, full, C):
+    """3x2 / (2, 1) / (1, 0) windows and the reverse on dyadic inputs: a maximum is exact; an average is an exact sum and ONE
+    division (exact where the window's clipped area is a power of two, correctly rounded elsewhere: half an ulp).  The plan reports
+    no kernel for a mover; launch_pool (misc.hip) takes the nine-loads kernel only `if (p.is_max && p.kh == 3 && p.kw == 3 &&
+    p.sh == 2 && p.sw == 2)`, so these run pool_kernel."""
+    assert k[0] != k[1] and s[0] != s[1] and p[0] != p[1]
+    x_v = R.pool_dyadic_inputs(C)
+    ref, S = R.pool64(x_v, kind, k, s, p, full)
+    b, x, y = pool_plan(C, k, s, p, full, kind)
+    res = run(ctx, b, {}, {"X": put(filled(6, b, "X"), x, x_v)}, ["Y"])
+    got = view_of(b, res, "Y", y)
+    if kind == "max":
+        np.testing.assert_array_equal(got, ref)
+    else:
+        exact = ref.astype(np.float32) == ref
+        assert exact.any() and not exact.all()
+        np.testing.assert_array_equal(got[exact], ref[exact])
+        assert (np.abs(got - ref) <= U * np.abs(ref)).all()
 
 
 @pytest.mark.parametrize("C", R.POOL_C)

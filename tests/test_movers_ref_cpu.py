@@ -7,6 +7,7 @@ import pytest
 import movers_ref as R
 from movers_ref import U
 from oracle import ops as O
+from plan_helpers import pair
 
 nchw = lambda a: np.ascontiguousarray(np.asarray(a).transpose(0, 3, 1, 2))
 nhwc = lambda a: np.ascontiguousarray(np.asarray(a).transpose(0, 2, 3, 1))
@@ -19,9 +20,10 @@ def oracle_warp(feat, flow):
 def oracle_cols(x, off, k, s, p, d, dg):
     """O.deform_im2col image by image, as (N, Ho, Wo, taps, C)"""
     N, H, W, C = x.shape
-    Ho, Wo = R.conv_out(H, k, s, p, d), R.conv_out(W, k, s, p, d)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = pair(k), pair(s), pair(p), pair(d)
+    Ho, Wo = R.conv_out(H, kh, sh, ph, dh), R.conv_out(W, kw, sw, pw, dw)
     xs, offs = nchw(x), nchw(off)
-    out = [O.deform_im2col(xs[n], offs[n], k, s, p, d, dg).reshape(C, k * k, Ho, Wo).transpose(2, 3, 1, 0) for n in range(N)]
+    out = [O.deform_im2col(xs[n], offs[n], k, s, p, d, dg).reshape(C, kh * kw, Ho, Wo).transpose(2, 3, 1, 0) for n in range(N)]
     return np.stack(out)
 
 
@@ -77,6 +79,45 @@ def test_dcn_cols_dyadic_inputs_are_exact_and_take_every_branch(case):
         assert R.dcn_blocks(case) == R.DCN_BLOCKS[i]
 
 
+PAIR_IDS = lambda c: "k%dx%ds%dx%dp%dx%dd%dx%ddg%d_c%d_%dx%d" % (pair(c[0]) + pair(c[1]) + pair(c[2]) + pair(c[3]) + tuple(c[4:8]))
+
+
+@pytest.mark.parametrize("case", R.DCN_PAIR_CASES, ids=PAIR_IDS)
+def test_dcn_cols_with_unequal_pairs_is_exact_takes_every_branch_and_is_grid_sample_inside(case):
+    """the reference with (h, w) pairs: bit for bit the oracle on the dyadic inputs of the GPU test, every branch of the rule taken
+    where the geometry has it (no padding above: no tap starts outside above without an offset, the offsets alone send them there),
+    and -- with every sample pulled inside the map, where DCN v1 and zero-padded bilinear interpolation are the same function --
+    torch.nn.functional.grid_sample in double"""
+    import torch
+    k, s, p, d, dg, C, H, W, _ = case
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = pair(k), pair(s), pair(p), pair(d)
+    assert kh != kw and ph != pw and dh != dw and (kh, kw) != (3, 3)
+    x, off = R.dcn_inputs(case)
+    ref, _, rec = R.dcn_cols64(x, off, k, s, p, d, dg)
+    assert np.array_equal(ref.astype(np.float32), ref)
+    np.testing.assert_array_equal(oracle_cols(x, off, k, s, p, d, dg), ref)
+    for what, n in R.branch_counts(rec).items():
+        assert n >= R.DCN_MIN_TAPS, (what, n)
+    N, Ho, Wo, taps = ref.shape[:4]
+    assert (Ho, Wo) == (R.conv_out(H, kh, sh, ph, dh), R.conv_out(W, kw, sw, pw, dw)) and taps == kh * kw
+    # interior: move every sample into [0, H - 1] x [0, W - 1]
+    o = off.astype(np.float64).reshape(N, Ho, Wo, dg, taps, 2)
+    i, j = np.arange(taps) // kw, np.arange(taps) % kw
+    py = (np.arange(Ho) * sh - ph).reshape(1, Ho, 1, 1, 1) + i * dh + o[..., 0]
+    px = (np.arange(Wo) * sw - pw).reshape(1, 1, Wo, 1, 1) + j * dw + o[..., 1]
+    o[..., 0] += np.clip(py, 0.0, H - 1.0) - py
+    o[..., 1] += np.clip(px, 0.0, W - 1.0) - px
+    py, px = np.clip(py, 0.0, H - 1.0), np.clip(px, 0.0, W - 1.0)
+    xg = R.gauss(77, N, H, W, C).astype(np.float64)
+    got = R.dcn_cols64(xg, o.reshape(off.shape), k, s, p, d, dg)[0]
+    xt, cpg = torch.from_numpy(nchw(xg)), C // dg
+    for g in range(dg):
+        for t in range(taps):
+            grid = torch.from_numpy(np.stack([px[:, :, :, g, t] / ((W - 1) / 2.0) - 1.0, py[:, :, :, g, t] / ((H - 1) / 2.0) - 1.0], axis=-1))
+            want = torch.nn.functional.grid_sample(xt[:, g * cpg:(g + 1) * cpg], grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+            assert np.abs(got[:, :, :, t, g * cpg:(g + 1) * cpg] - nhwc(want.numpy())).max() <= 1e-12 * np.abs(xg).max(), (g, t)
+
+
 def test_dcn_cases_cover_the_block_counts_and_both_kernels():
     assert sorted(R.DCN_BLOCKS.values()) == [1, 2, 7, 8, 9, 13]
     assert {c[:5] for c in R.DCN_CASES} == {(3, 1, 1, 1, 1), (3, 1, 2, 2, 4), (3, 2, 1, 1, 1), (1, 1, 0, 1, 2), (5, 1, 2, 1, 1)}
@@ -115,6 +156,28 @@ def test_pool64_matches_the_oracle(kind, k, s, p, full, C):
         np.testing.assert_array_equal(got, ref)
     else:
         assert (np.abs(got - ref) <= 5 * U * S).all()          # three sums and the division
+
+
+@pytest.mark.parametrize("C", R.POOL_C)
+@pytest.mark.parametrize("kind,k,s,p,full", R.POOL_PAIR_CASES)
+def test_pool64_with_unequal_pairs_matches_torch_and_the_oracle(kind, k, s, p, full, C):
+    """torch.nn.functional.max_pool2d / avg_pool2d (count_include_pad, as mx.symbol.Pooling counts) in double with the same pairs:
+    `valid` is ceil_mode=False; `full` is ceil_mode=True where that keeps the same number of windows.  The fp32 oracle: a maximum is
+    exact, a dyadic average is one correctly rounded division away."""
+    import torch
+    assert k[0] != k[1] and s[0] != s[1] and p[0] != p[1]
+    x = R.pool_dyadic_inputs(C)
+    ref, S = R.pool64(x, kind, k, s, p, full)
+    f = torch.nn.functional.max_pool2d if kind == "max" else torch.nn.functional.avg_pool2d
+    want = f(torch.from_numpy(nchw(x).astype(np.float64)), k, s, p, ceil_mode=full).numpy()
+    assert want.shape == nchw(ref).shape, "the case is one where both conventions keep the same windows"
+    assert np.abs(nchw(ref) - want).max() <= 1e-13 * np.abs(want).max()
+    got = nhwc(O.pool2d(nchw(x), kind, k, s, p, "full" if full else "valid"))
+    if kind == "max":
+        np.testing.assert_array_equal(got, ref)
+    else:
+        assert (np.abs(got - ref) <= U * np.abs(ref)).all()
+    assert R.pool64(x, kind, k, s, p, not full)[0].shape == ref.shape
 
 
 @pytest.mark.parametrize("C", R.POOL_C)
