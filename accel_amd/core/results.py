@@ -1,6 +1,7 @@
 """Finishing a frame on the GPU: the label map `mx.nd.argmax(logits)` returns, taken back to the source frame's size there and handed
 over as labels, as a colour image or as counts in a confusion matrix (csrc/results_u8.hip behind accel_model_labels_to_source /
-_labels_colour / _hist_add / _hist_read).
+_labels_colour / _hist_add / _hist_read) -- and the logits themselves finished as a per-pixel confidence (csrc/confidence.hip behind
+accel_model_confidence).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -14,12 +15,16 @@ import numpy as np
 from .. import runtime
 
 
-def _geometry(handle, like, hw=None):
+def _geometry(handle, like, hw=None, scores=False):
     """(n, out_h, out_w, h, w) of a finishing call.  `like`: a RawFrames array (its frames' size and the resize it stands for), a
     dict with out_h, out_w and h, w (other keys, such as those of RawFrames.geometry, are ignored; h, w default to `hw`), or None:
-    the whole H x W map is valid and is resized to `hw`."""
+    the whole H x W map is valid and is resized to `hw`.  scores: the handle is a logits handle, n x ncls x H x W."""
     shape = tuple(handle.shape)
-    if len(shape) != 3:
+    if scores:
+        if len(shape) != 4:
+            raise ValueError("a logits handle is n x ncls x H x W, got shape %s" % (shape,))
+        shape = (shape[0],) + shape[2:]
+    elif len(shape) != 3:
         raise ValueError("a label handle is n x H x W, got shape %s" % (shape,))
     n, H, W = shape
     if like is None:
@@ -37,15 +42,18 @@ def _geometry(handle, like, hw=None):
     return n, int(out_h), int(out_w), int(src[0]), int(src[1])
 
 
-def _model(handle):
-    """the model whose `labels` buffer the handle stands for -- still holding what the handle was made for, or AccelError"""
+def _model(handle, buffer="labels"):
+    """the model whose `buffer` (`labels`, or `logits`) the handle stands for -- still holding what the handle was made for, or AccelError"""
     ref = getattr(handle, "device_ref", None)
-    if not ref or ref[1] != "labels":
-        raise runtime.AccelError("not a label handle of the GPU path (mx.nd.argmax of a Predictor's logits): nothing to finish on the GPU")
+    if not ref or ref[1] != buffer:
+        if buffer == "labels":
+            raise runtime.AccelError("not a label handle of the GPU path (mx.nd.argmax of a Predictor's logits): nothing to finish on the GPU")
+        raise runtime.AccelError("not a %s handle of the GPU path (an output of Predictor.predict): nothing to finish on the GPU" % buffer)
     m, buf, gen = ref
     if m.generation(buf) != gen:
-        raise runtime.AccelError("this label handle is stale: its buffer has been written since (fetch it with .asnumpy(), or finish "
-                                 "the frame, before the next forward that writes labels)")
+        what = "label" if buffer == "labels" else buffer
+        raise runtime.AccelError("this %s handle is stale: its buffer has been written since (fetch it with .asnumpy(), or finish "
+                                 "the frame, before the next forward that writes %s)" % (what, buffer))
     return m
 
 
@@ -65,6 +73,31 @@ def colour(handle, like, palette, frames=None, alpha=256, rgb=True):
     if frames is True:
         frames = like.frames
     return m.labels_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
+
+
+def confidence(handle, like, margin=False, second=False, hist=False, probabilities=None):
+    """How sure the network was, per source pixel, from the LOGITS handle a Predictor returned (not the label handle): conf, numpy
+    n x h x w uint8 = min(255, floor(256 * largest softmax probability)) -- or the tuple (conf[, margin][, second][, hist]) with what
+    was asked for: margin n x h x w float32 = top score - runner-up score, second n x h x w uint8 = the runner-up class, hist
+    n x 256 uint64 = pixels per conf level of each frame (utils.image.confidence_host, on the GPU).  probabilities: the stored scores
+    are probabilities already (a tail lowered with softmax=1); None takes the answer from the handle."""
+    m = _model(handle, "logits")
+    n, out_h, out_w, h, w = _geometry(handle, like, scores=True)
+    if probabilities is None:
+        probabilities = bool(getattr(handle, "probabilities", False))
+    out = m.confidence(n, out_h, out_w, h, w, is_prob=probabilities, conf=True, margin=bool(margin), second=bool(second), hist=bool(hist))
+    out = tuple(a for a in out if a is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def confidence_summary(hist, level=128):
+    """(mean confidence as a probability: the centre of every level's interval weighted by its count; share of pixels below `level`)
+    of one frame's 256 counts"""
+    c = np.asarray(hist, np.float64).reshape(256)
+    total = c.sum()
+    if total <= 0:
+        return float("nan"), float("nan")
+    return float((c * (np.arange(256) + 0.5) / 256.0).sum() / total), float(c[:int(level)].sum() / total)
 
 
 def per_class_iu(hist):

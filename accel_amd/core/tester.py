@@ -252,6 +252,7 @@ class Predictor(object):
                 out[name] = arrays[d[6:]]
             elif d == "logits":
                 out[name] = self._logits_handle(N, H, W)
+                out[name].probabilities = bool(getattr(lw, "tail_softmax", False))      # the tail applied the softmax already
             else:
                 out[name] = self._feat_handle(N, H, W, getattr(getattr(d, "buf", None), "space", "feat"))
         return [out]

@@ -103,6 +103,8 @@ struct accel_model {
     // of a plan, or a `meta labels_n= labels_h= labels_w=` line, says it), a staging buffer for results on their way to the host, and the
     // confusion matrix: 32 x 32 unsigned 64-bit words that persist across calls, for ncls = hist_ncls classes (0: empty since the last clear)
     int labels_n = 0, labels_h = 0, labels_w = 0;
+    // accel_model_confidence: the shape of `logits` (n x ncls x H x W fp32), learnt the same way (`meta logits_n= logits_ncls= logits_h= logits_w=`)
+    int logits_n = 0, logits_ncls = 0, logits_h = 0, logits_w = 0;
     void* stage_out = nullptr;
     size_t stage_out_bytes = 0;
     unsigned long long* hist = nullptr;
@@ -340,6 +342,10 @@ static int parse_plan(accel_plan* p, const char* text)
         if (kind == "meta") {
             if (kv_has(kv, "feat_c")) { p->m->feat_c = (int)kv_int(kv, "feat_c"); p->m->feat_h = (int)kv_int(kv, "feat_h"); p->m->feat_w = (int)kv_int(kv, "feat_w"); p->m->feat_n = (int)kv_int(kv, "feat_n", 1); }
             if (kv_has(kv, "labels_h")) { p->m->labels_n = (int)kv_int(kv, "labels_n", 1); p->m->labels_h = (int)kv_int(kv, "labels_h"); p->m->labels_w = (int)kv_int(kv, "labels_w"); }
+            if (kv_has(kv, "logits_h")) {
+                p->m->logits_n = (int)kv_int(kv, "logits_n", 1); p->m->logits_ncls = (int)kv_int(kv, "logits_ncls", 19);
+                p->m->logits_h = (int)kv_int(kv, "logits_h"); p->m->logits_w = (int)kv_int(kv, "logits_w");
+            }
             continue;
         }
         if (kind == "arena") { p->arena_bytes = strtoull(kv_str(kv, "bytes", "0").c_str(), nullptr, 10); continue; }
@@ -1015,6 +1021,7 @@ static int finalize_op(accel_plan* p, Op& op)
         q.H = (int)kv_int(kv, "H"); q.W = (int)kv_int(kv, "W");
         if (q.H != 16 * q.Hs || q.W != 16 * q.Ws) return fail(ACCEL_ERR_PLAN, "score_tail: output must be 16x the score map");
         if (op.d.space == "labels") { p->m->labels_n = op.d.N; p->m->labels_h = q.H; p->m->labels_w = q.W; }      // what the finishing calls read
+        if (op.c.space == "logits") { p->m->logits_n = op.c.N; p->m->logits_ncls = q.ncls; p->m->logits_h = q.H; p->m->logits_w = q.W; }
         q.logits = op.c.ptr; q.labels = reinterpret_cast<unsigned char*>(op.d.ptr);
         const size_t wn = (size_t)q.ncls * 32 * 32;
         if ((rc = upload_param(p, kv_str(kv, "wl"), wn, &q.wl))) return rc;
@@ -2430,6 +2437,104 @@ extern "C" int accel_model_labels_colour(accel_model* m, int n, int out_h, int o
     HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)3 * w, (size_t)n * h, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+// ---- confidence of finished frames (confidence.hip) ----------------------------------------------------------------------------------------
+// What the two entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int confidence_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, const void* conf, size_t conf_pitch,
+                           const void* margin, size_t margin_pitch, const void* second, size_t second_pitch, const void* hist)
+{
+    if (!conf && !margin && !second && !hist) return fail(ACCEL_ERR_ARG, "%s: conf, margin, second and hist are all NULL: nothing to compute", fn);
+    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be 2, 19 or 21", fn, ncls);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    if (conf) if (int rc = pitch_arg(fn, "conf_pitch", conf_pitch, w, 1)) return rc;
+    if (margin) {
+        if (int rc = pitch_arg(fn, "margin_pitch", margin_pitch, w, 4)) return rc;
+        if (margin_pitch % 4) return fail(ACCEL_ERR_ARG, "%s: margin_pitch = %zu bytes, must be a multiple of 4", fn, margin_pitch);
+    }
+    if (second) if (int rc = pitch_arg(fn, "second_pitch", second_pitch, w, 1)) return rc;
+    return 0;
+}
+
+// the device side of a call whose results go to the host: tight rows in `base` (conf, second: n * h * w bytes; margin: 4 times that; hist: n * 256
+// words), each part 256-byte aligned
+struct ConfStage {
+    size_t conf = 0, second = 0, margin = 0, hist = 0, bytes = 0;
+    ConfStage(int n, int h, int w, bool c, bool mg, bool s, bool hi)
+    {
+        const size_t px = (size_t)n * h * w;
+        auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
+        if (c) conf = take(px);
+        if (s) second = take(px);
+        if (mg) margin = take(px * 4);
+        if (hi) hist = take((size_t)n * 256 * sizeof(uint64_t));
+    }
+};
+
+static int confidence_to_host(const char* fn, const float* scores, unsigned char* base, const ConfStage& cs, int n, int ncls, int H, int W, int out_h, int out_w,
+                              int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second,
+                              size_t second_pitch, uint64_t* hist, hipStream_t st)
+{
+    unsigned char* dc = conf ? base + cs.conf : nullptr;
+    unsigned char* ds = second ? base + cs.second : nullptr;
+    float* dm = margin ? reinterpret_cast<float*>(base + cs.margin) : nullptr;
+    unsigned long long* dh = hist ? reinterpret_cast<unsigned long long*>(base + cs.hist) : nullptr;
+    HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
+    if (conf) HIP_TRY(rows_to_host(conf, conf_pitch, dc, (size_t)w, (size_t)n * h, st));
+    if (second) HIP_TRY(rows_to_host(second, second_pitch, ds, (size_t)w, (size_t)n * h, st));
+    if (margin) HIP_TRY(rows_to_host(margin, margin_pitch, dm, (size_t)4 * w, (size_t)n * h, st));
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, dh, (size_t)n * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_scores_confidence(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
+                                       uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
+                                       uint64_t* hist)
+{
+    const char* fn = "accel_scores_confidence";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const ConfStage cs(n, h, w, conf, margin, second, hist);
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    return confidence_to_host(fn, s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                              hist, ctx->stream);
+}
+
+extern "C" int accel_model_confidence(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch,
+                                      float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist, int dst_on_device)
+{
+    const char* fn = "accel_model_confidence";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    auto it = m->pbufs.find("logits");
+    if (it == m->pbufs.end() || m->logits_h < 1 || m->logits_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: this model has no `logits` buffer of a known shape (no plan with a score_tail op is bound)", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    const int ncls = m->logits_ncls, H = m->logits_h, W = m->logits_w;
+    if (n > m->logits_n || (size_t)n * ncls * H * W * sizeof(float) > it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %d", fn, n, m->logits_n);
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
+    const float* scores = static_cast<const float*>(it->second.ptr);
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)margin);
+        if (reinterpret_cast<uintptr_t>(hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)hist);
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                                  reinterpret_cast<unsigned long long*>(hist), st));
+        return 0;
+    }
+    const ConfStage cs(n, h, w, conf, margin, second, hist);
+    unsigned char* base = nullptr;
+    if (int rc = stage_out(m, cs.bytes, &base)) return rc;
+    return confidence_to_host(fn, scores, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                              hist, st);
 }
 
 extern "C" int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes)

@@ -163,6 +163,13 @@ hipError_t launch_labels_hist(const unsigned char* labels, int n, int H, int W, 
                               int ncls, unsigned long long* hist, hipStream_t st);
 hipError_t launch_labels_colour(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, const unsigned char* palette_rgb,
                                 int rgb_order, const unsigned char* frame, size_t frame_pitch, int alpha, unsigned char* dst, size_t dst_pitch, hipStream_t st);
+// confidence of finished frames (confidence.hip): n x ncls x H x W fp32 scores (NCHW, the layout of `logits`; ncls in {2, 19, 21}) in the geometry
+// above -> per source pixel conf = min(255, floor(256 * largest softmax probability)) (float64; is_prob: the scores are probabilities, no
+// exponential), margin = l_top1 - l_top2 (fp32), second = the runner-up class, and hist = n x 256 counts of the conf levels per frame (overwritten).
+// A null output is left out; pitches in bytes (margin_pitch a multiple of 4).  All pointers are device memory; the kernel only reads `scores`
+hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob, unsigned char* conf,
+                             size_t conf_pitch, float* margin, size_t margin_pitch, unsigned char* second, size_t second_pitch, unsigned long long* hist,
+                             hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

@@ -182,6 +182,10 @@ def main(argv=None):
                     help='finish every frame on the GPU: the timed loop fetches the labels at the SOURCE frame\'s size (padding and '
                          'resize undone there), the confusion matrix of the mIoU accumulates in HBM and --out writes those labels; '
                          'with --raw-frames this evaluates frames of any size against ground truth of their own size')
+    ap.add_argument('--confidence', action='store_true',
+                    help='with --finish-on-gpu: per frame, the mean confidence (largest softmax probability) and the share of pixels '
+                         'below level 128 of 256, from a histogram made on the GPU where the logits are; --out also writes '
+                         'conf_<frame>.png in greyscale')
     ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
                                                  '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
@@ -192,6 +196,8 @@ def main(argv=None):
         raise ValueError("Invalid interval %d - must be >=1" % interv)
     if num_ex < 1:
         raise ValueError("Invalid num_ex %d - must be >=1" % num_ex)
+    if args.confidence and not args.finish_on_gpu:
+        raise ValueError("--confidence needs --finish-on-gpu")
     if args.cfg:
         update_config(args.cfg)
     num_classes = config.dataset.NUM_CLASSES
@@ -249,7 +255,7 @@ def main(argv=None):
     hist = np.zeros((num_classes, num_classes))
     for idx, arrays in enumerate(data):
         tic()
-        _, lab = runner.step(idx, arrays, interv)
+        lg, lab = runner.step(idx, arrays, interv)
         if idx + 1 < len(data) and not args.pageable:
             runner.prefetch(data[idx + 1])        # next frame starts crossing PCIe while this one computes
         if args.finish_on_gpu:
@@ -260,6 +266,14 @@ def main(argv=None):
         time_sum += elapsed
         count += 1
         print('testing {} {:.4f}s [{:.4f}s]'.format(names[idx], elapsed, time_sum / count))
+        if args.confidence:       # after the clock: the histogram is 2 KB, the map a byte per source pixel
+            conf, conf_hist = results.confidence(lg, source, hist=True)
+            mean, low = results.confidence_summary(conf_hist[0])
+            print('confidence mean {:.4f} below-128 {:.4f}'.format(mean, low))
+            if args.out:
+                from PIL import Image
+                os.makedirs(args.out, exist_ok=True)
+                Image.fromarray(conf[0]).save(os.path.join(args.out, 'conf_' + os.path.basename(names[idx])))
         if args.out:
             from PIL import Image
             from .dataset.cityscape import getpallete

@@ -151,6 +151,7 @@ class Lowering(object):
         self.absorbed = set()
         self.concat_slot = {}  # id(node) -> View inside a concat buffer
         self.outputs = {}      # output name -> descriptor
+        self.tail_softmax = False      # the lowered score tail carries softmax=1: `logits` holds probabilities
         self.ncls = ncls
         self.total_flops = 0.0
         self.cons = {}
@@ -761,6 +762,7 @@ class Lowering(object):
             flops = 2.0 * ncls * 2 * ncls * self.H * self.W
         if softmax is not None:
             args["softmax"] = 1      # SoftmaxOutput(multi_output=True) at test time: softmax over the class axis
+        self.tail_softmax = softmax is not None      # `logits` holds probabilities (core.results.confidence reads it off the handle)
         self.emit("score_tail", args, reads, [], flops=flops, nbytes=4.0 * ncls * self.H * self.W + self.H * self.W, n=nb)
         for n in [node] + list(crops) + ups + ([corr] if corr is not None else []) + ([softmax] if softmax is not None else []):
             self.absorbed.add(id(n))

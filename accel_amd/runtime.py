@@ -84,6 +84,8 @@ def _declare(lib):
         "accel_model_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
         "accel_model_hist_read": [vp, vp, i, i],
         "accel_model_labels_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
+        "accel_scores_confidence": [vp, vp, i, i, i, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp],
+        "accel_model_confidence": [vp, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp, i],
         "accel_comm_available": [],
         "accel_comm_unique_id": [vp],
         "accel_comm_create": [vp, i, i, vp, c.POINTER(vp)],
@@ -221,6 +223,31 @@ def _result_rows(out, n, h, w, channels):
     return out, out.shape[2]
 
 
+def _confidence_outputs(n, h, w, conf, margin, second, hist):
+    """the destinations of a confidence call: for conf, margin and second True (a fresh tight array), False / None (left out) or the
+    caller's array of n x h x pitch elements (uint8, for margin float32: pitch * 4 bytes per row), of which only the first w of every
+    row are written; `hist` True or False.  Returns ([conf, margin, second, hist], [(pointer, pitch in bytes)] of the first three,
+    hist pointer), with None / (None, 0) for what is left out."""
+    outs, ptrs = [], []
+    for want, dtype, what in ((conf, np.uint8, "conf"), (margin, np.float32, "margin"), (second, np.uint8, "second")):
+        if want is None or want is False:
+            outs.append(None)
+            ptrs.append((None, 0))
+            continue
+        if want is True:
+            a = np.empty((n, h, w), dtype)
+        else:
+            a = want
+            if a.dtype != dtype or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 3 or a.shape[:2] != (n, h):
+                raise ValueError("%s must be a writeable C-contiguous %s array of n x h x pitch = %d x %d x pitch elements"
+                                 % (what, np.dtype(dtype).name, n, h))
+        outs.append(a)
+        ptrs.append((_fp(a), a.shape[2] * a.itemsize))
+    hs = np.zeros((n, 256), np.uint64) if hist else None
+    outs.append(hs)
+    return outs, ptrs, None if hs is None else _fp(hs)
+
+
 class Context(object):
     def __init__(self, device_id=0):
         self.handle = ctypes.c_void_p()
@@ -356,6 +383,19 @@ class Context(object):
         check(lib().accel_labels_colour(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)),
                                         int(bool(rgb)), None if f is None else _fp(f), fp, int(alpha), _fp(out), pitch))
         return out
+
+    def scores_confidence(self, scores, out_h, out_w, h, w, is_prob=False, conf=True, margin=True, second=True, hist=True):
+        """accel_scores_confidence: n x ncls x H x W scores whose valid region is out_h x out_w -> (conf, margin, second, hist) at the
+        source size h x w (utils.image.confidence_host); each of conf / margin / second is True, False (left out: None is returned
+        in its place) or an array of n x h x pitch elements to write the rows into; hist True or False"""
+        a = _f32(scores)
+        if a.ndim != 4:
+            raise ValueError("scores must be n x ncls x H x W fp32, got shape %s" % (a.shape,))
+        n, ncls, H, W = a.shape
+        outs, p, hp = _confidence_outputs(n, int(h), int(w), conf, margin, second, hist)
+        check(lib().accel_scores_confidence(self.handle, _fp(a), n, ncls, H, W, int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                            p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], hp))
+        return tuple(outs)
 
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
@@ -651,6 +691,22 @@ class Model(object):
         check(lib().accel_model_labels_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
                                               ctypes.c_void_p(frame_ptr) if frame_ptr else None, int(frame_pitch), int(alpha), 1,
                                               ctypes.c_void_p(dst_ptr), int(pitch), 1))
+
+    def confidence(self, n, out_h, out_w, h, w, is_prob=False, conf=True, margin=True, second=True, hist=True):
+        """accel_model_confidence: (conf, margin, second, hist) of the first n frames of `logits` at the source size h x w, as numpy
+        arrays (see Context.scores_confidence for the arguments); it only READS `logits`"""
+        outs, p, hp = _confidence_outputs(int(n), int(h), int(w), conf, margin, second, hist)
+        check(lib().accel_model_confidence(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                           p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], hp, 0))
+        return tuple(outs)
+
+    def confidence_device(self, n, out_h, out_w, h, w, is_prob=False, conf_ptr=None, conf_pitch=0, margin_ptr=None, margin_pitch=0,
+                          second_ptr=None, second_pitch=0, hist_ptr=None):
+        """the same into caller-owned HBM (enqueued, no host wait): device pointers, pitches in bytes; hist_ptr names n x 256 uint64"""
+        vp = lambda v: ctypes.c_void_p(v) if v else None
+        check(lib().accel_model_confidence(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                           vp(conf_ptr), int(conf_pitch), vp(margin_ptr), int(margin_pitch), vp(second_ptr), int(second_pitch),
+                                           vp(hist_ptr), 1))
 
     def read_async(self, buf, pinned):
         """enqueue the download of `buf` into a PinnedBuffer on the compute stream; valid after ctx.sync()"""

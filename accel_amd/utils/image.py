@@ -105,6 +105,42 @@ def colour_host(labels, palette, frames=None, alpha=256, rgb=True):
     return np.ascontiguousarray(out)
 
 
+def confidence_host(scores, out_h, out_w, h, w, is_prob=False):
+    """The specification of accel_scores_confidence, in float64: scores n x ncls x H x W fp32 (valid region out_h x out_w in the
+    top-left corner) -> (conf, margin, second, hist) at the source size h x w, pixel for pixel where labels_to_source_host puts
+    the labels.
+      conf    uint8    min(255, floor(256 * p)), p = 1 / sum_k exp(l_k - l_max) the largest softmax probability (classes summed in
+                       ascending order); is_prob: the scores are probabilities already, min(255, floor(256 * float64(top1)))
+      margin  float32  l_top1 - l_top2: one fp32 subtraction of two stored values, 0 on a tie at the top
+      second  uint8    the first maximal index among the classes other than `best`, the first-max argmax
+      hist    uint64   n x 256: the number of source pixels of each frame at each conf level"""
+    s = np.asarray(scores, np.float32)
+    if s.ndim != 4 or s.shape[1] < 2:
+        raise ValueError("scores must be n x ncls x H x W with ncls >= 2, got shape %s" % (s.shape,))
+    ys, xs = nearest_index(h, out_h), nearest_index(w, out_w)
+    s = np.ascontiguousarray(s[:, :, :int(out_h), :int(out_w)][:, :, ys, :][:, :, :, xs])
+    n, ncls = s.shape[:2]
+    best = np.argmax(s, axis=1)                                   # the first maximal index
+    top1 = np.take_along_axis(s, best[:, None], axis=1)[:, 0]
+    is_best = np.arange(ncls).reshape(1, ncls, 1, 1) == best[:, None]
+    others = np.where(is_best, -np.inf, s)
+    # (a class at -inf can still be the runner-up: when every other class is at -inf the first of them is)
+    second = np.argmax((others == others.max(axis=1, keepdims=True)) & ~is_best, axis=1)
+    top2 = np.take_along_axis(s, second[:, None], axis=1)[:, 0]
+    with np.errstate(invalid="ignore"):
+        margin = (top1 - top2).astype(np.float32)
+    if is_prob:
+        scaled = 256.0 * top1.astype(np.float64)
+    else:
+        total = np.zeros(top1.shape, np.float64)
+        for k in range(ncls):
+            total += np.exp(s[:, k].astype(np.float64) - top1.astype(np.float64))
+        scaled = 256.0 * (1.0 / total)
+    conf = np.minimum(255.0, np.floor(scaled)).astype(np.uint8)
+    hist = np.stack([np.bincount(c.reshape(-1), minlength=256) for c in conf]).astype(np.uint64)
+    return conf, margin, second.astype(np.uint8), hist
+
+
 def transform(im, pixel_means):
     """Contract of lib/utils/image.py:224-235: a BGR H x W x 3 frame becomes the 1 x 3 x H x W RGB tensor with the per-channel
     mean removed (`pixel_means` is given in B, G, R order like the frame).  float64 like the reference; arrays become fp32

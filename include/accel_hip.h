@@ -248,6 +248,37 @@ int accel_model_labels_colour(accel_model* m, int n, int out_h, int out_w, int h
                               const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
                               uint8_t* dst, size_t dst_pitch, int dst_on_device);
 
+/* ---- finished frames: per-pixel confidence ------------------------------------------------------------------------
+ * How sure the network was, made where the scores are (csrc/confidence.hip) instead of `logits.asnumpy()` plus a softmax
+ * on the host.  `scores` is n x ncls x H x W fp32 (NCHW, the layout of `logits`), ncls in {2, 19, 21}; the geometry is
+ * that of the block above (valid region out_h x out_w, source size h x w, the same integer nearest rule), so every output
+ * lines up pixel for pixel with accel_labels_to_source.  Per source pixel, any subset of (a NULL pointer leaves one out):
+ *   conf     n x h x w uint8    min(255, floor(256 * p)), p = 1 / sum_k exp(l_k - l_max) the largest softmax probability;
+ *                               differences, exp, sum (classes in ascending order), reciprocal and scaling in float64
+ *   margin   n x h x w fp32     l_top1 - l_top2, one fp32 subtraction of two stored values; top2 is the largest value among
+ *                               the classes other than the winner: 0 on a tie at the top
+ *   second   n x h x w uint8    the runner-up: the first maximal index among the classes other than `best`, the first-max
+ *                               argmax (= `labels`)
+ *   hist     n x 256 uint64     per frame, the number of source pixels at each conf level: OVERWRITTEN, exact, independent
+ *                               of the order of arrival (any threshold and the mean confidence follow on the host)
+ * is_prob = 1: the stored values are probabilities already (a tail lowered with softmax=1): conf =
+ * min(255, floor(256 * double(top1))), no exponential; margin and second as above, on the stored values.
+ * Rows are `*_pitch` BYTES apart (>= a row; margin_pitch a multiple of 4), h * pitch from frame to frame; bytes between
+ * rows are not written.  Argument errors (a NULL input, all outputs NULL, a size < 1 or > 32768, out_h > H, out_w > W, a
+ * pitch smaller than a row, a misaligned margin pitch, an unsupported ncls, n larger than the bound batch, no `logits`
+ * buffer) return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_scores_confidence     operator level: host scores in, host results out (the parity tests)
+ *   accel_model_confidence      the same on the model's `logits` buffer (n, ncls, H, W as the bound plans write it),
+ *                               enqueued on the context stream after the run that wrote it.  It only reads `logits`: no
+ *                               write generation changes, no captured graph is touched.  A host destination
+ *                               (dst_on_device = 0) is filled when the call returns, device destinations (= 1: all of
+ *                               them, margin 4-byte and hist 8-byte aligned) when the stream reaches it */
+int accel_scores_confidence(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
+                            uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
+                            uint64_t* hist);
+int accel_model_confidence(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch,
+                           float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist, int dst_on_device);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
