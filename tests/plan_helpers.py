@@ -1,5 +1,6 @@
 """Hand-written plans for the operator tests: NHWC views of the arena, a builder of plan text (import_nchw -> convolutions -> export_nchw
-with every launch geometry forced; or the byte movers of csrc/misc.hip between sub-views of canvases the host writes and reads raw)
+with every launch geometry forced; or the byte movers of csrc/misc.hip between sub-views of canvases the host writes and reads raw;
+half arena buffers and the reader of their raw bytes),
 a float64 convolution and deconvolution, and the BatchNorm constants of the convolution tests.  No tests in here."""
 import numpy as np
 
@@ -14,21 +15,27 @@ def pair(v):
 
 
 class V(object):
-    """an NHWC view of the arena: offset, channels, channel stride, H, W, images"""
+    """an NHWC view of the arena: offset, channels, channel stride, H, W, images; half: 2-byte elements (":h"); base: the byte offset
+    of the buffer the view lies in (its first pixel's channel 0)"""
 
-    def __init__(self, off, C, Cs, H, W, N, space="A", half=False):
-        self.off, self.C, self.Cs, self.H, self.W, self.N, self.space, self.half = off, C, Cs, H, W, N, space, half
+    def __init__(self, off, C, Cs, H, W, N, space="A", half=False, base=0):
+        self.off, self.C, self.Cs, self.H, self.W, self.N, self.space, self.half, self.base = off, C, Cs, H, W, N, space, half, base
 
     def ref(self):
         return "%s:%d:%d:%d:%d:%d:%d%s" % (self.space, self.off, self.C, self.Cs, self.H, self.W, self.N, ":h" if self.half else "")
 
-    def sub(self, c0, C):
-        return V(self.off + 4 * c0, C, self.Cs, self.H, self.W, self.N, self.space)
+    @property
+    def esize(self):
+        return 2 if self.half else 4
+
+    def sub(self, c0, C, N=None):
+        """channels [c0, c0 + C) of the view's pixels (c0 counts elements: 2 bytes each in a half view), of its first N images"""
+        return V(self.off + self.esize * c0, C, self.Cs, self.H, self.W, self.N if N is None else N, self.space, self.half, self.base)
 
     @property
     def c0(self):
-        """first channel of the view inside its buffer's pixel stride (fp32 views that start in the buffer's first pixel)"""
-        return self.off // 4
+        """first channel of the view inside its buffer's pixel stride (views that start in the buffer's first pixel)"""
+        return (self.off - self.base) // self.esize
 
 
 class Builder(object):
@@ -40,6 +47,14 @@ class Builder(object):
     def buf(self, C, H, W, Cs=None):
         v = V(self.arena, C, Cs or r4(C), H, W, self.N)
         self.arena += al(self.N * H * W * v.Cs * 4)
+        return v
+
+    def hbuf(self, Cs, H, W, N=None):
+        """a HALF arena buffer of N images, as the view of its whole width Cs (Cs % 8 == 0); the host cannot write it: a convolution
+        of the plan does, and half_words() reads it back"""
+        N = self.N if N is None else N
+        v = V(self.arena, Cs, Cs, H, W, N, half=True, base=self.arena)
+        self.arena += al(N * H * W * Cs * 2)
         return v
 
     def inp(self, name, C, H, W, Cs=None, yr=None):
@@ -156,6 +171,12 @@ class Builder(object):
 
     def text(self):
         return "\n".join(["option " + " ".join(self.options), "arena bytes=%d" % max(self.arena, 256)] + self.head + self.lines) + "\n"
+
+
+def half_words(arena, v):
+    """the half buffer a view v lies in (Builder.hbuf) as (N, H, W, Cs) uint16, from the raw bytes of the arena (Plan.arena())"""
+    n = v.N * v.H * v.W * v.Cs * 2
+    return arena[v.base:v.base + n].view(np.uint16).reshape(v.N, v.H, v.W, v.Cs)
 
 
 def canary_words(n):
