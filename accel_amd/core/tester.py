@@ -26,7 +26,7 @@ import numpy as np
 
 from .. import lower as _lower
 from .. import runtime
-from ..mx.ndarray import DeviceArray, RawFrames
+from ..mx.ndarray import DeviceArray, NV12Frames, RawFrames
 
 _MODELS = {}   # (device id, N, H, W, parameter token, owner) -> runtime.Model: the key and cur plans of one demo share buffers
 
@@ -210,7 +210,9 @@ class Predictor(object):
         tag = _uid(arrays["data"])
         if tag is None or res.get("data") != tag:
             if tag is not None and pre.get("data") == tag:
-                if isinstance(data, RawFrames):      # its BYTES were prefetched (uint8 shadow): converted on the way into `data`
+                if isinstance(data, NV12Frames):     # its BYTES were prefetched (the same uint8 shadow): colour conversion included
+                    m.commit_nv12("data", *_nv12_layout(data), **data.geometry)
+                elif isinstance(data, RawFrames):    # its BYTES were prefetched (uint8 shadow): converted on the way into `data`
                     m.commit_u8("data", *_u8_layout(data), **data.geometry)
                 else:
                     m.commit("data")
@@ -298,7 +300,7 @@ class Predictor(object):
         pb = getattr(data_array, "pinned", None)
         if pb is None or self._model is None:
             return False
-        if isinstance(data_array, RawFrames):       # uint8 frames: a quarter of the bytes cross PCIe, into a shadow of their own
+        if isinstance(data_array, RawFrames):       # uint8 bytes, BGR or NV12: a quarter or an eighth of the fp32 tensor crosses PCIe, into a shadow of their own
             self._model.prefetch_u8("data", pb)
         else:
             self._model.prefetch("data", pb)
@@ -325,10 +327,20 @@ def _u8_layout(raw):
     return n, h, w, 3 * w, raw.means
 
 
+def _nv12_layout(raw):
+    """(n, h, w, pitch, uv_offset, frame_bytes, colour, means) of an NV12Frames array, as Model.commit_nv12 takes them"""
+    lay = raw.layout
+    return lay["n"], lay["h"], lay["w"], lay["pitch"], lay["uv_offset"], lay["frame_bytes"], lay["colour"], raw.means
+
+
 def _write_image(m, buf, arr):
     """an image input that is not in HBM yet: raw uint8 frames are uploaded as bytes and resized / centred / padded by the GPU
-    (accel_model_write_u8), anything else is the fp32 tensor itself"""
-    if isinstance(arr, RawFrames):
+    (accel_model_write_u8; NV12 bytes: accel_model_write_nv12, which converts the colour too), anything else is the fp32 tensor itself"""
+    if isinstance(arr, NV12Frames):
+        lay = arr.layout
+        m.write_nv12(buf, arr.nv12, lay["h"], lay["w"], arr.means, pitch=lay["pitch"], uv_offset=lay["uv_offset"], frame_bytes=lay["frame_bytes"],
+                     colour=lay["colour"], **arr.geometry)
+    elif isinstance(arr, RawFrames):
         m.write_u8(buf, arr.frames, arr.means, **arr.geometry)
     else:
         m.write(buf, _host(arr))

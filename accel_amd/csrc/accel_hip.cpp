@@ -2053,6 +2053,18 @@ extern "C" int accel_model_commit(accel_model* m, const char* buf)
 }
 
 // ---- uint8 frames ---------------------------------------------------------------------------------------------------------------
+// The resize a frame conversion is told (out_h, out_w, step) and the padded size H x W, for an h x w source: shared by the BGR and the NV12 route.
+static int frame_resize_args(const char* fn, int h, int w, int out_h, int out_w, double step, int H, int W)
+{
+    if (!(step > 0.0) || step > 1e9) return fail(ACCEL_ERR_ARG, "%s: step = %g, must be a positive number of source pixels per output pixel", fn, step);
+    if (H < 1 || W < 1) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be >= 1", fn, H, W);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    if (step == 1.0 && (out_h != h || out_w != w))
+        return fail(ACCEL_ERR_ARG, "%s: step = 1 copies the frame, but out_h x out_w = %d x %d is not h x w = %d x %d", fn, out_h, out_w, h, w);
+    return 0;
+}
+
 // Geometry of a uint8 frame conversion, checked before anything is enqueued: every message names the argument at fault.
 static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
                          int H, int W)
@@ -2063,13 +2075,7 @@ static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, s
     if (h < 1) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be >= 1", fn, h);
     if (w < 1) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be >= 1", fn, w);
     if (pitch < (size_t)3 * w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %zu", fn, pitch, w, (size_t)3 * w);
-    if (!(step > 0.0) || step > 1e9) return fail(ACCEL_ERR_ARG, "%s: step = %g, must be a positive number of source pixels per output pixel", fn, step);
-    if (H < 1 || W < 1) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be >= 1", fn, H, W);
-    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
-    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
-    if (step == 1.0 && (out_h != h || out_w != w))
-        return fail(ACCEL_ERR_ARG, "%s: step = 1 copies the frame, but out_h x out_w = %d x %d is not h x w = %d x %d", fn, out_h, out_w, h, w);
-    return 0;
+    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
 }
 
 static int frame_u8_buf(const char* fn, accel_model* m, const char* buf, int n, int H, int W, DevBuf** out)
@@ -2174,6 +2180,158 @@ extern "C" int accel_model_commit_u8(accel_model* m, const char* buf, int n, int
     if (int rc = unbind(m, *b)) return rc;
     HIP_TRY(launch_frames_u8(static_cast<const unsigned char*>(sh->second.ptr), n, h, w, pitch, means_bgr, out_h, out_w, step, H, W,
                              static_cast<float*>(b->ptr), m->ctx->stream));
+    HIP_TRY(hipEventRecord(sh->second.consumed, m->ctx->stream));
+    sh->second.was_consumed = true;
+    sh->second.filled = 0;
+    m->source_written(buf);
+    return 0;
+}
+
+// ---- NV12 frames (frames_nv12.hip) ------------------------------------------------------------------------------------------------
+extern "C" int accel_nv12_coefficients(int colour, int32_t out[6])
+{
+    if (!out) return fail(ACCEL_ERR_ARG, "accel_nv12_coefficients: out is NULL");
+    const int32_t* c = nv12_coefficients(colour);
+    if (!c) return fail(ACCEL_ERR_ARG, "accel_nv12_coefficients: colour = %d, must be in 0 .. 3", colour);
+    for (int i = 0; i < 6; ++i) out[i] = c[i];
+    return 0;
+}
+
+// Layout of NV12 frames, checked before anything is enqueued: every message names the argument at fault.
+static int nv12_layout_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour)
+{
+    const int lim = 32768;
+    if (!nv12) return fail(ACCEL_ERR_ARG, "%s: nv12 is NULL", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (h < 2 || h > lim || h % 2) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be even and in 2 .. %d", fn, h, lim);
+    if (w < 2 || w > lim || w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 2 .. %d", fn, w, lim);
+    if (pitch < (size_t)w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %d", fn, pitch, w, w);
+    if (pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, pitch);
+    if (uv_offset < (size_t)h * pitch)
+        return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, uv_offset, h, pitch, (size_t)h * pitch);
+    if (uv_offset > ((size_t)1 << 60)) return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes is not an offset into a frame", fn, uv_offset);
+    if (frame_bytes < uv_offset + (size_t)(h / 2) * pitch)
+        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the chroma plane at uv_offset = %zu ends at %zu", fn, frame_bytes, uv_offset,
+                    uv_offset + (size_t)(h / 2) * pitch);
+    if (frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, frame_bytes);
+    if (colour < 0 || colour > 3) return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, colour);
+    return 0;
+}
+
+static int frame_nv12_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                           const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    if (int rc = nv12_layout_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
+}
+
+// the bytes n frames occupy: the last one ends with its chroma plane
+static size_t nv12_bytes(int n, int h, size_t pitch, size_t uv_offset, size_t frame_bytes)
+{
+    return (size_t)(n - 1) * frame_bytes + uv_offset + (size_t)(h / 2) * pitch;
+}
+
+extern "C" int accel_frame_nv12(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* out)
+{
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_nv12: NULL argument");
+    if (int rc = frame_nv12_args("accel_frame_nv12", nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t sb = nv12_bytes(n, h, pitch, uv_offset, frame_bytes), ob = (size_t)n * 3 * H * W * 4;
+    unsigned char* s = nullptr;
+    float* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&s, sb));
+    if (hipMalloc((void**)&d, ob) != hipSuccess) { hipFree(s); return fail(ACCEL_ERR_HIP, "accel_frame_nv12: hipMalloc of %zu bytes failed", ob); }
+    int rc = 0;
+    if (hipMemcpy(s, nv12, sb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_nv12: H2D copy failed");
+    if (!rc && launch_frames_nv12(s, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, d, ctx->stream) != hipSuccess)
+        rc = fail(ACCEL_ERR_HIP, "accel_frame_nv12: launch failed");
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_nv12: sync failed");
+    if (!rc && hipMemcpy(out, d, ob, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_frame_nv12: D2H copy failed");
+    hipFree(s); hipFree(d);
+    return rc;
+}
+
+extern "C" int accel_nv12_to_bgr(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                 uint8_t* bgr_out, size_t out_pitch, int on_device)
+{
+    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: NULL argument");
+    if (int rc = nv12_layout_args("accel_nv12_to_bgr", nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
+    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: bgr_out is NULL");
+    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
+        return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on_device) {
+        HIP_TRY(launch_nv12_to_bgr(nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, bgr_out, out_pitch, ctx->stream));
+        return 0;
+    }
+    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
+    const size_t sb = nv12_bytes(n, h, pitch, uv_offset, frame_bytes), ob = (size_t)n * h * (size_t)3 * w;
+    unsigned char *s = nullptr, *d = nullptr;
+    HIP_TRY(hipMalloc((void**)&s, sb));
+    if (hipMalloc((void**)&d, ob) != hipSuccess) { hipFree(s); return fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: hipMalloc of %zu bytes failed", ob); }
+    int rc = 0;
+    if (hipMemcpy(s, nv12, sb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: H2D copy failed");
+    if (!rc && launch_nv12_to_bgr(s, n, h, w, pitch, uv_offset, frame_bytes, colour, d, (size_t)3 * w, ctx->stream) != hipSuccess)
+        rc = fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: launch failed");
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: sync failed");
+    if (!rc && hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: D2H copy failed");
+    hipFree(s); hipFree(d);
+    return rc;
+}
+
+extern "C" int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset,
+                                      size_t frame_bytes, int colour, const double* means_bgr, int out_h, int out_w, double step, int H, int W,
+                                      int src_on_device)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_nv12: NULL argument");
+    if (int rc = frame_nv12_args("accel_model_write_nv12", nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf("accel_model_write_nv12", m, buf, n, H, W, &b)) return rc;
+    const unsigned char* src = nv12;
+    if (!src_on_device) {
+        const size_t sb = nv12_bytes(n, h, pitch, uv_offset, frame_bytes);
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        if (m->stage_u8_bytes < sb) {
+            // (hipFree waits for the device: no conversion kernel is still reading the old staging buffer)
+            if (m->stage_u8) { HIP_TRY(hipFree(m->stage_u8)); m->stage_u8 = nullptr; m->stage_u8_bytes = 0; }
+            HIP_TRY(hipMalloc(&m->stage_u8, sb));
+            m->stage_u8_bytes = sb;
+        }
+        HIP_TRY(hipMemcpyAsync(m->stage_u8, nv12, sb, hipMemcpyHostToDevice, m->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(m->ctx->stream));   // pageable source may be reused by the caller
+        src = static_cast<const unsigned char*>(m->stage_u8);
+    }
+    if (int rc = unbind(m, *b)) return rc;
+    HIP_TRY(launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(b->ptr),
+                               m->ctx->stream));
+    m->source_written(buf);
+    return 0;
+}
+
+// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow: bytes are bytes)
+extern "C" int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                       const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: unknown buffer '%s'", buf);
+    auto sh = m->shadows_u8.find(buf);
+    if (sh == m->shadows_u8.end() || !sh->second.filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_nv12_args("accel_model_commit_nv12", sh->second.ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W))
+        return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf("accel_model_commit_nv12", m, buf, n, H, W, &b)) return rc;
+    const size_t need = nv12_bytes(n, h, pitch, uv_offset, frame_bytes);
+    if (need > sh->second.filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: (n - 1) x frame_bytes + uv_offset + h/2 x pitch = %zu bytes, %zu were prefetched for '%s'",
+                    need, sh->second.filled, buf);
+    HIP_TRY(hipStreamWaitEvent(m->ctx->stream, sh->second.ready, 0));
+    if (int rc = unbind(m, *b)) return rc;
+    HIP_TRY(launch_frames_nv12(static_cast<const unsigned char*>(sh->second.ptr), n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w,
+                               step, H, W, static_cast<float*>(b->ptr), m->ctx->stream));
     HIP_TRY(hipEventRecord(sh->second.consumed, m->ctx->stream));
     sh->second.was_consumed = true;
     sh->second.filled = 0;

@@ -11,41 +11,21 @@
 // A bandwidth kernel: 3 bytes read and 12 written per pixel.  No range slot: the tensor is read by prep_rgb / prep_flow, which raise
 // the slots of what they write.
 #include "kernels.h"
+#include "frames_resample.h"
 #include <stdint.h>
 
 namespace {
 
-struct Means { double b, g, r; };
+using frames::Means;
+using frames::centred;
 
-// One grey level of the resized image: _resize_bilinear of utils/image.py for channel c of output pixel (x, y).  Every operation is
-// an IEEE double operation rounded on its own (hipcc contracts a*b + c into an fma in device code by default; numpy does not).
-__device__ __forceinline__ int resample(const unsigned char* __restrict__ img, size_t pitch, int h, int w, int x, int y, int c, double step)
+// One grey level of the resized image: _resize_bilinear of utils/image.py for channel c of output pixel (x, y), whose taps are `t`
+// (frames_resample.h holds the arithmetic, shared with frames_nv12.hip).
+__device__ __forceinline__ int resample(const unsigned char* __restrict__ img, size_t pitch, const frames::Taps& t, int c)
 {
-#pragma clang fp contract(off)
-    double sy = ((double)y + 0.5) * step - 0.5;
-    double sx = ((double)x + 0.5) * step - 0.5;
-    sy = fmin(fmax(sy, 0.0), (double)(h - 1));
-    sx = fmin(fmax(sx, 0.0), (double)(w - 1));
-    const int y0 = (int)floor(sy), x0 = (int)floor(sx);
-    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-    const double fy = sy - (double)y0, fx = sx - (double)x0;
-    const unsigned char* r0 = img + (size_t)y0 * pitch + c;
-    const unsigned char* r1 = img + (size_t)y1 * pitch + c;
-    const double a00 = (double)r0[3 * x0], a01 = (double)r0[3 * x1];
-    const double a10 = (double)r1[3 * x0], a11 = (double)r1[3 * x1];
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    const double t0 = a00 * gx, t1 = a01 * fx;
-    const double top = t0 + t1;
-    const double b0 = a10 * gx, b1 = a11 * fx;
-    const double bot = b0 + b1;
-    const double u0 = top * gy, u1 = bot * fy;
-    const double v = fmin(fmax(rint(u0 + u1), 0.0), 255.0);
-    return (int)v;
-}
-
-__device__ __forceinline__ float centred(int grey, double mean)
-{
-    return (float)((double)grey - mean);       // exact difference (both are doubles with few bits), one rounding to fp32
+    const unsigned char* r0 = img + (size_t)t.y0 * pitch + c;
+    const unsigned char* r1 = img + (size_t)t.y1 * pitch + c;
+    return frames::blend((double)r0[3 * t.x0], (double)r0[3 * t.x1], (double)r1[3 * t.x0], (double)r1[3 * t.x1], t);
 }
 
 // step == 1: a thread takes 4 consecutive pixels of a row.  FAST: w % 4 == 0, pitch % 4 == 0 and a 4-byte aligned source -- the 12
@@ -105,9 +85,10 @@ __global__ __launch_bounds__(256) void frames_u8_resample_kernel(const unsigned 
     const size_t plane = (size_t)H * W;
     int b = 0, g = 0, r = 0;
     if (y < out_h && x < out_w) {
-        b = resample(img, pitch, h, w, x, y, 0, step);
-        g = resample(img, pitch, h, w, x, y, 1, step);
-        r = resample(img, pitch, h, w, x, y, 2, step);
+        const frames::Taps t = frames::taps(h, w, x, y, step);
+        b = resample(img, pitch, t, 0);
+        g = resample(img, pitch, t, 1);
+        r = resample(img, pitch, t, 2);
     }
     out[0] = centred(r, mean.r);
     out[plane] = centred(g, mean.g);

@@ -152,6 +152,15 @@ hipError_t launch_set_slot(const void** slot, const void* value, hipStream_t st)
 // bytes themselves, out_h == h and out_w == w), mean removed in float64, padding = fp32(-mean); bit for bit utils/image.py
 hipError_t launch_frames_u8(const unsigned char* src, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
                             int H, int W, float* dst, hipStream_t st);
+// NV12 frames (frames_nv12.hip): n frames in device memory, each h rows of w luma bytes `pitch` apart from byte 0 and, at byte `uv_offset`, h / 2
+// rows of w / 2 (Cb, Cr) pairs at the same pitch, `frame_bytes` from frame to frame (h, w even) -> the tensor launch_frames_u8 writes for the BGR
+// frames image.nv12_to_bgr_host makes of them (`colour` 0 .. 3: BT.601 / BT.709, limited / full range; integer arithmetic, replicated chroma),
+// bit for bit -- and those BGR bytes themselves, rows `out_pitch` apart.  nv12_coefficients: the six integers of a colour mode, or nullptr.
+const int32_t* nv12_coefficients(int colour);
+hipError_t launch_frames_nv12(const unsigned char* src, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                              const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* dst, hipStream_t st);
+hipError_t launch_nv12_to_bgr(const unsigned char* src, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                              unsigned char* dst, size_t out_pitch, hipStream_t st);
 // finished frames (results_u8.hip): n label maps of H x W bytes (valid region out_h x out_w, top left) taken to the source size h x w by the
 // integer nearest rule labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)] -- as labels (rows `dst_pitch` apart), as counts added
 // to an ncls x ncls matrix of 64-bit words (rows gt, columns prediction, ids >= ncls ignored; ncls <= 32), or as n x h x w x 3 colours

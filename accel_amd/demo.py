@@ -22,7 +22,7 @@ import numpy as np
 from . import mx
 from .config.config import config, update_config
 from .core.tester import Predictor, im_segment
-from .utils.image import resize, transform
+from .utils.image import NV12_COLOURS, bgr_to_nv12_host, resize, transform
 from .utils.tictoc import tic, toc
 
 
@@ -65,7 +65,7 @@ def get_symbols(version, cfg):
     return inst, inst.get_key_test_symbol(cfg), inst.get_cur_test_symbol(cfg)
 
 
-def build_batches(frames_bgr, cfg, pinned=False, raw=False):
+def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None):
     """demo.py:165-190: list of [data, data_key, feat_key] arrays per frame.
 
     One array per frame serves as this frame's `data` and as the next frame's `data_key` (the reference builds two
@@ -73,12 +73,19 @@ def build_batches(frames_bgr, cfg, pinned=False, raw=False):
     uploaded one call earlier and copies the image inside HBM instead of sending it over PCIe twice.
     pinned=True places the images in page-locked memory (mx.cpu_pinned()), the source of overlapped uploads.
     raw=True keeps every frame as its uint8 BGR bytes (mx.nd.raw_frames): no fp32 image is built on the host, a quarter of
-    the bytes cross PCIe and the GPU resizes, removes the mean and pads (accel_model_write_u8)."""
+    the bytes cross PCIe and the GPU resizes, removes the mean and pads (accel_model_write_u8).
+    nv12=<colour mode> (utils.image.NV12_COLOURS) feeds every frame as NV12 bytes (mx.nd.nv12_frames), as a video decoder would hand it
+    out -- bgr_to_nv12_host stands in for the decoder; an eighth of the bytes cross PCIe and the GPU converts the colour as well."""
     data, prev = [], None
     ctx = mx.cpu_pinned() if pinned else None
     zero_feat = mx.nd.array(np.zeros((1, cfg.network.DFF_FEAT_DIM, 1, 1)))
     for im in frames_bgr:
-        if raw:
+        if nv12 is not None:
+            h, w = im.shape[:2]
+            if h % 2 or w % 2:
+                raise ValueError("--nv12: NV12 frames have an even height and width, this frame is %d x %d (odd-sized)" % (h, w))
+            cur = mx.nd.nv12_frames(bgr_to_nv12_host(im, nv12), h, w, cfg, colour=nv12, ctx=ctx)
+        elif raw:
             cur = mx.nd.raw_frames(im, cfg, ctx=ctx)
         else:
             target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
@@ -178,6 +185,10 @@ def main(argv=None):
     ap.add_argument('--raw-frames', dest='raw_frames', action='store_true',
                     help='upload the frames as uint8 BGR bytes and resize / mean-subtract / pad them on the GPU: no fp32 image '
                          'is built on the host')
+    ap.add_argument('--nv12', nargs='?', const='bt601', default=None, choices=sorted(NV12_COLOURS),
+                    help='feed the frames as NV12 bytes, the format video decoders hand out (implies --raw-frames): the frames, of even '
+                         'height and width, are turned into NV12 on the host (standing in for a decoder) and the GPU converts the colour '
+                         'with the named matrix, resizes, mean-subtracts and pads')
     ap.add_argument('--finish-on-gpu', dest='finish_on_gpu', action='store_true',
                     help='finish every frame on the GPU: the timed loop fetches the labels at the SOURCE frame\'s size (padding and '
                          'resize undone there), the confusion matrix of the mIoU accumulates in HBM and --out writes those labels; '
@@ -198,6 +209,8 @@ def main(argv=None):
         raise ValueError("Invalid num_ex %d - must be >=1" % num_ex)
     if args.confidence and not args.finish_on_gpu:
         raise ValueError("--confidence needs --finish-on-gpu")
+    if args.nv12:
+        args.raw_frames = True
     if args.cfg:
         update_config(args.cfg)
     num_classes = config.dataset.NUM_CLASSES
@@ -227,6 +240,8 @@ def main(argv=None):
         config.SCALES[0] = tuple(int(v) for v in args.scales.split('x'))
     from .utils import load_model, synth
     H, W = frames[0].shape[:2]
+    if args.nv12 and (H % 2 or W % 2):
+        raise ValueError("--nv12: NV12 frames have an even height and width, these frames are %d x %d (odd-sized)" % (H, W))
     if args.finish_on_gpu:    # how a label map goes back to a frame: the valid region of the bound size and the frame's own size
         from .core import results
         from .utils.image import resize_geometry
@@ -246,7 +261,7 @@ def main(argv=None):
         print('no --params given: seeded random weights (throughput is valid, mIoU is meaningless)')
         arg_params, aux_params = synth.model_params(version, H, W, config)
 
-    data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames)
+    data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames, nv12=args.nv12)
     runner = ClipRunner(version, config, arg_params, aux_params, (H, W))
     for j in range(min(2, len(data))):       # warm up (demo.py:207-220)
         runner.step(j, data[j], interv)[1].asnumpy()

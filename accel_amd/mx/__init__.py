@@ -8,14 +8,15 @@ import types as _types
 from . import operator
 from . import symbol
 from . import symbol as sym
-from .ndarray import DataBatch, DeviceArray, RawFrames, array, argmax, raw_frames, zeros
+from .ndarray import DataBatch, DeviceArray, NV12Frames, RawFrames, array, argmax, nv12_frames, raw_frames, zeros
 
 contrib = _types.SimpleNamespace(
     symbol=_types.SimpleNamespace(DeformableConvolution=symbol.DeformableConvolution),
     sym=_types.SimpleNamespace(DeformableConvolution=symbol.DeformableConvolution))
 io = _types.SimpleNamespace(DataBatch=DataBatch)
 sym.split = symbol.split
-nd = _types.SimpleNamespace(array=array, argmax=argmax, zeros=zeros, NDArray=DeviceArray, raw_frames=raw_frames, RawFrames=RawFrames)
+nd = _types.SimpleNamespace(array=array, argmax=argmax, zeros=zeros, NDArray=DeviceArray, raw_frames=raw_frames, RawFrames=RawFrames,
+                            nv12_frames=nv12_frames, NV12Frames=NV12Frames)
 ndarray = nd
 
 

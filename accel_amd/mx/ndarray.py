@@ -129,6 +129,71 @@ def raw_frames(frames_bgr_u8, cfg, ctx=None):
     return RawFrames(frames_bgr_u8, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, ctx=ctx)
 
 
+class NV12Frames(RawFrames):
+    """Video frames as a decoder hands them out -- NV12: a luma plane and a half-size plane of interleaved Cb, Cr -- standing for the same
+    image tensor as the RawFrames of their BGR conversion (utils.image.nv12_to_bgr_host): a Predictor uploads the BYTES, 1.5 per pixel,
+    and the GPU converts the colour, resizes, removes the mean and pads (accel_model_write_nv12 / _prefetch_u8 / _commit_nv12).
+    `.nv12` holds the bytes (n x frame_bytes), `.layout` what the C ABI is told about them; `.frames` is the BGR conversion computed on the
+    host on first use, for consumers that want the picture (core.results), and `.asnumpy()` the tensor computed from it."""
+
+    def __init__(self, buf, h, w, pixel_means, target_size, max_size, stride=0, colour="bt601", pitch=None, uv_offset=None, frame_bytes=None, ctx=None):
+        from ..utils import image
+        if isinstance(buf, (list, tuple)):
+            if len({np.shape(f) for f in buf}) != 1:
+                raise ValueError("all frames of one NV12 array must have the same number of bytes")
+            buf = np.stack([np.asarray(f).reshape(-1) for f in buf])
+            frame_bytes = buf.shape[1] if frame_bytes is None else frame_bytes
+        elif np.ndim(buf) == 2 and frame_bytes is None:
+            frame_bytes = np.shape(buf)[1]
+        lay = image.nv12_layout(h, w, pitch, uv_offset, frame_bytes)
+        a = image.nv12_bytes(buf, lay)
+        n = a.shape[0]
+        pb = None
+        if ctx is not None and getattr(ctx, "device_type", "") == "cpu_pinned":
+            from .. import runtime
+            pb = runtime.PinnedBuffer(a.shape, np.uint8)
+            pb.array[...] = a
+            nv12 = pb.array
+        else:
+            nv12 = np.array(a, order="C", copy=True)      # a copy, like mx.nd.array: later edits of the source do not reach it
+        nv12.setflags(write=False)
+        h, w = lay["h"], lay["w"]
+        scale, out_h, out_w, H, W = image.resize_geometry(h, w, target_size, max_size, stride)
+        DeviceArray.__init__(self, shape=(n, 3, H, W), fetch=self._host_tensor, pinned=pb)
+        self.nv12 = nv12
+        self.layout = dict(n=n, colour=image.nv12_colour(colour), **lay)
+        self._frames = None
+        self.means = tuple(float(v) for v in np.asarray(pixel_means, np.float64).reshape(-1))
+        self.resize_args = (target_size, max_size, stride)
+        self.scale = scale
+        self.geometry = dict(out_h=out_h, out_w=out_w, step=image.resample_step(h, w, scale, out_h, out_w), H=H, W=W)
+
+    @property
+    def frames(self):
+        """the frames as uint8 n x h x w x 3 BGR, converted on the host on first use"""
+        if self._frames is None:
+            from ..utils import image
+            lay = self.layout
+            f = image.nv12_to_bgr_host(self.nv12, lay["h"], lay["w"], lay["pitch"], lay["uv_offset"], lay["frame_bytes"], lay["colour"])
+            f.setflags(write=False)
+            self._frames = f
+        return self._frames
+
+    def __repr__(self):
+        return "<NV12Frames %dx%dx%d for %s>" % (self.layout["n"], self.layout["h"], self.layout["w"], "x".join(map(str, self._shape)))
+
+
+def nv12_frames(buf, h, w, cfg, colour="bt601", pitch=None, uv_offset=None, ctx=None):
+    """NV12 frames of h x w pixels (uint8 bytes: one flat frame, n x frame_bytes, a flat run of whole frames, or a list of frames) for a
+    Predictor: converted with `colour` (utils.image.NV12_COLOURS), resized to cfg.SCALES[0], centred on cfg.network.PIXEL_MEANS and padded
+    to cfg.network.IMAGE_STRIDE on the GPU.  pitch: bytes per row (default w); uv_offset: where the chroma plane starts (default
+    h * pitch); the bytes from frame to frame are the row length of an n x frame_bytes buffer, else those of one tightly laid-out frame.
+    Always a COPY of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
+    target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
+    return NV12Frames(buf, h, w, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, colour=colour, pitch=pitch,
+                      uv_offset=uv_offset, ctx=ctx)
+
+
 def zeros(shape, ctx=None, dtype=np.float32):
     return DeviceArray(host=np.zeros(shape, dtype))
 

@@ -77,6 +77,11 @@ def _declare(lib):
         "accel_model_write_u8": [vp, c.c_char_p, vp, i, i, i, sz, vp, i, i, c.c_double, i, i, i],
         "accel_model_prefetch_u8": [vp, c.c_char_p, vp, sz],
         "accel_model_commit_u8": [vp, c.c_char_p, i, i, i, sz, vp, i, i, c.c_double, i, i],
+        "accel_nv12_coefficients": [i, c.POINTER(c.c_int32)],
+        "accel_frame_nv12": [vp, vp, i, i, i, sz, sz, sz, i, vp, i, i, c.c_double, i, i, vp],
+        "accel_nv12_to_bgr": [vp, vp, i, i, i, sz, sz, sz, i, vp, sz, i],
+        "accel_model_write_nv12": [vp, c.c_char_p, vp, i, i, i, sz, sz, sz, i, vp, i, i, c.c_double, i, i, i],
+        "accel_model_commit_nv12": [vp, c.c_char_p, i, i, i, sz, sz, sz, i, vp, i, i, c.c_double, i, i],
         "accel_labels_to_source": [vp, vp, i, i, i, i, i, i, i, vp, sz],
         "accel_labels_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, vp],
         "accel_labels_colour": [vp, vp, i, i, i, i, i, i, i, vp, i, vp, sz, i, vp, sz],
@@ -185,6 +190,21 @@ def _u8_frames(frames, width=None):
     if a.ndim != 4 or a.shape[3] != 3:
         raise ValueError("frames must be n x h x w x 3 uint8 (BGR), got shape %s" % (a.shape,))
     return a, a.shape[0], a.shape[1], a.shape[2], 3 * a.shape[2]
+
+
+def _nv12_frames(buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+    """NV12 bytes as the C ABI takes them: (contiguous n x frame_bytes array, (n, h, w, pitch, uv_offset, frame_bytes, colour))"""
+    from .utils import image
+    lay = image.nv12_layout(h, w, pitch, uv_offset, frame_bytes)
+    a = np.ascontiguousarray(image.nv12_bytes(buf, lay))
+    return a, (a.shape[0], lay["h"], lay["w"], lay["pitch"], lay["uv_offset"], lay["frame_bytes"], image.nv12_colour(colour))
+
+
+def nv12_coefficients(colour):
+    """accel_nv12_coefficients: the six integers (yoff, ky, krv, kgu, kgv, kbu) of colour mode 0 .. 3 as the library holds them (no GPU)"""
+    out = (ctypes.c_int32 * 6)()
+    check(lib().accel_nv12_coefficients(int(colour), out))
+    return tuple(int(v) for v in out)
 
 
 def _means3(means_bgr):
@@ -350,6 +370,28 @@ class Context(object):
         check(lib().accel_frame_u8(self.handle, _fp(a), n, h, w, pitch, _means3(means_bgr), int(out_h), int(out_w), float(step),
                                    int(H), int(W), _fp(out)))
         return out
+
+    def frame_nv12(self, buf, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+        """accel_frame_nv12: NV12 bytes (uint8, flat or n x frame_bytes; see utils.image.nv12_layout) -> the n x 3 x H x W fp32 tensor
+        transform(resize(nv12_to_bgr_host(..))) gives on the host"""
+        a, lay = _nv12_frames(buf, h, w, pitch, uv_offset, frame_bytes, colour)
+        out = np.empty((lay[0], 3, int(H), int(W)), np.float32)
+        check(lib().accel_frame_nv12(self.handle, _fp(a), *lay, _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W), _fp(out)))
+        return out
+
+    def nv12_to_bgr(self, buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0, out=None):
+        """accel_nv12_to_bgr: NV12 bytes -> n x h x w x 3 uint8 BGR (utils.image.nv12_to_bgr_host, on the GPU); `out`: n x h x pitch
+        bytes to write the rows into instead"""
+        a, lay = _nv12_frames(buf, h, w, pitch, uv_offset, frame_bytes, colour)
+        out, out_pitch = _result_rows(out, lay[0], lay[1], lay[2], 3)
+        check(lib().accel_nv12_to_bgr(self.handle, _fp(a), *lay, _fp(out), out_pitch, 0))
+        return out
+
+    def nv12_to_bgr_device(self, src_ptr, dst_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, out_pitch):
+        """the same from HBM into HBM (a decoder's output for a viewer, or for the blend of a colour image): only enqueued on the
+        context's stream; the caller keeps the source unchanged until the kernel has run"""
+        check(lib().accel_nv12_to_bgr(self.handle, ctypes.c_void_p(src_ptr), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
+                                      int(colour), ctypes.c_void_p(dst_ptr), int(out_pitch), 1))
 
     def labels_to_source(self, labels, out_h, out_w, h, w, out=None):
         """accel_labels_to_source: n x H x W label maps whose valid region is out_h x out_w -> n x h x w labels at the source size
@@ -644,6 +686,27 @@ class Model(object):
         self.__dict__.get("_resident", {}).pop(buf, None)
         check(lib().accel_model_commit_u8(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), _means3(means_bgr),
                                           int(out_h), int(out_w), float(step), int(H), int(W)))
+
+    def write_nv12(self, buf, nv12, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+        """accel_model_write_nv12: host NV12 bytes (see Context.frame_nv12) converted on the GPU into the image input `buf`"""
+        a, lay = _nv12_frames(nv12, h, w, pitch, uv_offset, frame_bytes, colour)
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_nv12(self.handle, buf.encode(), _fp(a), *lay, _means3(means_bgr), int(out_h), int(out_w), float(step),
+                                           int(H), int(W), 0))
+
+    def write_nv12_device(self, buf, dev_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W):
+        """the same with the bytes already in HBM (a decoder's output, a torch uint8 tensor's data_ptr()): read in place; the
+        caller keeps them unchanged until the kernel has run"""
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_nv12(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), int(h), int(w), int(pitch), int(uv_offset),
+                                           int(frame_bytes), int(colour), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W), 1))
+
+    def commit_nv12(self, buf, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W):
+        """accel_model_commit_nv12: the compute stream waits for prefetch_u8 (NV12 bytes go through the uint8 shadow), then the kernel
+        converts the shadow into `buf`"""
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_commit_nv12(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
+                                            int(colour), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W)))
 
     # ---- finished frames: they only READ `labels` (no generation changes) ------------------------------------------------------
     def labels_to_source(self, n, out_h, out_w, h, w, out=None):

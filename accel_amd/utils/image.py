@@ -147,3 +147,125 @@ def transform(im, pixel_means):
     when they are handed to the predictor (demo.py:186)."""
     centred = np.asarray(im, np.float64) - np.asarray(pixel_means, np.float64).reshape(1, 1, 3)
     return np.ascontiguousarray(centred[:, :, ::-1].transpose(2, 0, 1))[None]
+
+
+# ---- NV12 frames ------------------------------------------------------------------------------------------------------------------------------
+# What a video decoder hands out: h rows of w luma bytes, then h/2 rows of w/2 interleaved (Cb, Cr) byte pairs, every row `pitch` bytes
+# apart; the chroma plane starts at byte `uv_offset` of the frame and frame i at byte i * frame_bytes.  h and w are even.
+NV12_COLOURS = {"bt601": 0, "bt601-full": 1, "bt709": 2, "bt709-full": 3}
+
+
+def nv12_colour(colour):
+    """the number 0 .. 3 of a colour mode given by name (NV12_COLOURS) or by number"""
+    if isinstance(colour, str):
+        if colour not in NV12_COLOURS:
+            raise ValueError("colour = %r, must be one of %s" % (colour, ", ".join(sorted(NV12_COLOURS))))
+        return NV12_COLOURS[colour]
+    if isinstance(colour, (int, np.integer)) and not isinstance(colour, bool) and 0 <= int(colour) <= 3:
+        return int(colour)
+    raise ValueError("colour = %r, must be in 0 .. 3 or one of %s" % (colour, ", ".join(sorted(NV12_COLOURS))))
+
+
+def _nv12_standard(colour):
+    """(Kr, Kg, Kb, luma offset, luma scale, chroma scale) of a colour mode: BT.601 or BT.709, limited (16 .. 235 / 16 .. 240) or full range"""
+    c = nv12_colour(colour)
+    kr, kb = (0.299, 0.114) if c < 2 else (0.2126, 0.0722)
+    limited = c in (0, 2)
+    return kr, 1.0 - kr - kb, kb, (16 if limited else 0), (255.0 / 219.0 if limited else 1.0), (255.0 / 224.0 if limited else 1.0)
+
+
+def nv12_matrix(colour):
+    """the standard's own float64 values (yoff, ky, krv, kgu, kgv, kbu): R = ky (Y - yoff) + krv (Cr - 128), G = ky (Y - yoff) - kgu (Cb - 128)
+    - kgv (Cr - 128), B = ky (Y - yoff) + kbu (Cb - 128)"""
+    kr, kg, kb, yoff, ky, s = _nv12_standard(colour)
+    krv, kbu = 2.0 * (1.0 - kr) * s, 2.0 * (1.0 - kb) * s
+    return yoff, ky, krv, kbu * kb / kg, krv * kr / kg, kbu
+
+
+def nv12_coefficients(colour):
+    """(yoff, ky, krv, kgu, kgv, kbu) of the integer rule: round(65536 x the standard's value); what accel_nv12_coefficients returns"""
+    m = nv12_matrix(colour)
+    return (m[0],) + tuple(int(round(65536.0 * v)) for v in m[1:])
+
+
+def nv12_layout(h, w, pitch=None, uv_offset=None, frame_bytes=None):
+    """The layout dict the C ABI takes (h, w, pitch, uv_offset, frame_bytes), checked: tightly packed where nothing is given -- pitch = w,
+    the chroma plane right behind the luma plane, the next frame right behind the chroma plane."""
+    h, w = int(h), int(w)
+    if h < 2 or h > 32768 or h % 2:
+        raise ValueError("h = %d, must be even and in 2 .. 32768" % h)
+    if w < 2 or w > 32768 or w % 2:
+        raise ValueError("w = %d, must be even and in 2 .. 32768" % w)
+    pitch = w if pitch is None else int(pitch)
+    if pitch < w:
+        raise ValueError("pitch = %d bytes, a row of w = %d pixels has %d" % (pitch, w, w))
+    uv_offset = h * pitch if uv_offset is None else int(uv_offset)
+    if uv_offset < h * pitch:
+        raise ValueError("uv_offset = %d bytes, the luma plane ends at %d" % (uv_offset, h * pitch))
+    end = uv_offset + (h // 2) * pitch
+    frame_bytes = end if frame_bytes is None else int(frame_bytes)
+    if frame_bytes < end:
+        raise ValueError("frame_bytes = %d, the chroma plane ends at %d" % (frame_bytes, end))
+    return dict(h=h, w=w, pitch=pitch, uv_offset=uv_offset, frame_bytes=frame_bytes)
+
+
+def nv12_bytes(buf, layout):
+    """`buf` (uint8, flat or n x frame_bytes) as an n x frame_bytes array of whole frames, or ValueError"""
+    a = np.asarray(buf)
+    if a.dtype != np.uint8:
+        raise ValueError("NV12 bytes must be uint8, got %s" % a.dtype)
+    fb = layout["frame_bytes"]
+    if a.ndim not in (1, 2) or a.size == 0 or a.size % fb or (a.ndim == 2 and a.shape[1] != fb):
+        raise ValueError("NV12 bytes must be flat or n x frame_bytes = n x %d, got shape %s" % (fb, a.shape))
+    return a.reshape(-1, fb)
+
+
+def yuv_to_bgr(y, cb, cr, colour=0):
+    """The integer rule, the specification of csrc/frames_nv12.hip: arrays of Y, Cb, Cr bytes -> (B, G, R) uint8 arrays.  With c = Y - yoff,
+    d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts: R = clip((ky c + krv e + 32768) >> 16), G = clip((ky c - kgu d - kgv e +
+    32768) >> 16), B = clip((ky c + kbu d + 32768) >> 16)."""
+    yoff, ky, krv, kgu, kgv, kbu = nv12_coefficients(colour)
+    c = ky * (np.asarray(y).astype(np.int32) - yoff) + 32768
+    d = np.asarray(cb).astype(np.int32) - 128
+    e = np.asarray(cr).astype(np.int32) - 128
+    clip = lambda v: np.clip(v >> 16, 0, 255).astype(np.uint8)
+    return clip(c + kbu * d), clip(c - kgu * d - kgv * e), clip(c + krv * e)
+
+
+def nv12_to_bgr_host(buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+    """The specification of accel_nv12_to_bgr, and with resize + transform behind it of accel_frame_nv12: NV12 bytes (uint8, flat or
+    n x frame_bytes) -> n x h x w x 3 uint8 BGR.  Pixel (x, y) takes Y at (x, y) and Cb, Cr at (x >> 1, y >> 1) (replicated chroma) through
+    yuv_to_bgr.  Bytes in the gaps -- between rows, between the planes, after a frame -- are not interpreted."""
+    lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes)
+    h, w, pitch, uv_offset = lay["h"], lay["w"], lay["pitch"], lay["uv_offset"]
+    a = nv12_bytes(buf, lay)
+    n = a.shape[0]
+    luma = a[:, :h * pitch].reshape(n, h, pitch)[:, :, :w]
+    uv = a[:, uv_offset:uv_offset + (h // 2) * pitch].reshape(n, h // 2, pitch)[:, :, :w].reshape(n, h // 2, w // 2, 2)
+    up = lambda p: np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)
+    return np.ascontiguousarray(np.stack(yuv_to_bgr(luma, up(uv[..., 0]), up(uv[..., 1]), colour), axis=-1))
+
+
+def bgr_to_nv12_host(frames, colour=0):
+    """Tightly packed NV12 bytes (n x h * w * 3 / 2 uint8) of uint8 BGR frames ([n x] h x w x 3, h and w even): the standard's forward matrix
+    in float64, chroma the mean of each 2 x 2 block, rint, clip.  A tool for fabricating inputs (the demo's stand-in for a decoder), NOT the
+    specification of anything on the GPU, and not an inverse of nv12_to_bgr_host."""
+    f = np.asarray(frames)
+    if f.ndim == 3:
+        f = f[None]
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3:
+        raise ValueError("frames must be uint8 n x h x w x 3 (BGR), got %s %s" % (f.dtype, f.shape))
+    n, h, w = f.shape[:3]
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError("NV12 frames have an even height and width, got %d x %d" % (h, w))
+    kr, kg, kb, yoff, ky, s = _nv12_standard(colour)
+    b, g, r = (f[..., i].astype(np.float64) for i in range(3))
+    y = kr * r + kg * g + kb * b
+    block = lambda p: p.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4))
+    cb = 128.0 + block((b - y) / (2.0 * (1.0 - kb))) / s
+    cr = 128.0 + block((r - y) / (2.0 * (1.0 - kr))) / s
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    out = np.empty((n, h * w * 3 // 2), np.uint8)
+    out[:, :h * w] = q(yoff + y / ky).reshape(n, h * w)
+    out[:, h * w:] = np.stack([q(cb), q(cr)], axis=-1).reshape(n, h * w // 2)
+    return out

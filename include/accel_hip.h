@@ -200,6 +200,48 @@ int accel_model_prefetch_u8(accel_model* m, const char* buf, const void* pinned_
 int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, const double* means_bgr,
                           int out_h, int out_w, double step, int H, int W);
 
+/* ---- NV12 video frames -------------------------------------------------------------------------------------------
+ * What a hardware or software video decoder hands out: a full-size 8-bit luma plane followed by a half-height plane of
+ * interleaved Cb, Cr at half resolution.  The bytes are uploaded as they are (1.5 per pixel) and one kernel
+ * (csrc/frames_nv12.hip) converts the colour, resizes, removes the mean and pads: the tensor is, bit for bit,
+ * transform(resize(nv12_to_bgr_host(frame))) of accel_amd/utils/image.py -- what the uint8 route above gives for the
+ * BGR frames the conversion below makes.
+ *   nv12, n, h, w         n frames; h and w are even, 2 .. 32768
+ *   pitch                 bytes from row to row, in both planes (>= w)
+ *   uv_offset             the byte of a frame at which its h/2 rows of w/2 (Cb, Cr) pairs begin (>= h * pitch)
+ *   frame_bytes           bytes from frame to frame (>= uv_offset + (h/2) * pitch); n frames occupy
+ *                         (n - 1) * frame_bytes + uv_offset + (h/2) * pitch bytes.  Bytes in the gaps -- between rows,
+ *                         between the planes, after a frame -- are never read
+ *   colour                0 BT.601 limited range, 1 BT.601 full range, 2 BT.709 limited range, 3 BT.709 full range
+ *   means_bgr .. W        as for uint8 frames
+ * Pixel (x, y) takes Y at (x, y) and Cb, Cr at (x >> 1, y >> 1) (replicated chroma; interpolated chroma siting is not
+ * offered).  With c = Y - yoff, d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts:
+ *     R = clip((ky*c + krv*e         + 32768) >> 16, 0, 255)
+ *     G = clip((ky*c - kgu*d - kgv*e + 32768) >> 16, 0, 255)
+ *     B = clip((ky*c + kbu*d         + 32768) >> 16, 0, 255)
+ * (yoff, ky, krv, kgu, kgv, kbu) = round(65536 x the standard's value).  When the frame is resized, each of the four
+ * taps is converted to B, G, R bytes first and the bilinear arithmetic of the uint8 route runs on them.
+ * Argument errors return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_nv12_coefficients  the six integers (yoff, ky, krv, kgu, kgv, kbu) of a colour mode; host only, touches no GPU
+ *   accel_frame_nv12         operator level: host bytes in, host tensor out (the parity tests)
+ *   accel_nv12_to_bgr        n x h x w x 3 BGR bytes, rows `out_pitch` apart (>= 3 * w; bytes between rows are not
+ *                            written) and h * out_pitch from frame to frame.  on_device = 0: host in, host out;
+ *                            on_device = 1: both pointers are HBM and the kernel is only enqueued on the context's stream
+ *   accel_model_write_nv12   accel_model_write_u8 for NV12 bytes (src_on_device = 1: a decoder's output in HBM, read in
+ *                            place; the caller keeps it unchanged until the kernel has run)
+ *   accel_model_commit_nv12  accel_model_commit_u8 for NV12 bytes that accel_model_prefetch_u8 uploaded -- bytes are
+ *                            bytes, the uint8 shadow serves both (the bytes n frames occupy <= the bytes prefetched) */
+int accel_nv12_coefficients(int colour, int32_t out[6]);
+int accel_frame_nv12(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                     const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* out);
+int accel_nv12_to_bgr(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                      uint8_t* bgr_out, size_t out_pitch, int on_device);
+int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset,
+                           size_t frame_bytes, int colour, const double* means_bgr, int out_h, int out_w, double step, int H, int W,
+                           int src_on_device);
+int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                            const double* means_bgr, int out_h, int out_w, double step, int H, int W);
+
 /* ---- finished frames: labels at the source size, confusion matrix, colour image ------------------------------------
  * The output side of the loop (demo.py:245-266: `.asnumpy()` of the label map, fast_hist, the palette PNG) on the GPU
  * (csrc/results_u8.hip).  A label map is n x H x W uint8; its valid (unpadded) region is out_h x out_w in the top-left
