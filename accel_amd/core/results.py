@@ -1,7 +1,8 @@
 """Finishing a frame on the GPU: the label map `mx.nd.argmax(logits)` returns, taken back to the source frame's size there and handed
 over as labels, as a colour image or as counts in a confusion matrix (csrc/results_u8.hip behind accel_model_labels_to_source /
 _labels_colour / _hist_add / _hist_read) -- and the logits themselves finished as a per-pixel confidence (csrc/confidence.hip behind
-accel_model_confidence).
+accel_model_confidence), or as labels of their own: `interpolate=True` takes the LOGITS handle, interpolates the scores bilinearly to the
+source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -57,21 +58,30 @@ def _model(handle, buffer="labels"):
     return m
 
 
-def labels_at_source(handle, like):
-    """The labels of `handle` at the source frames' size: numpy n x h x w uint8 (utils.image.labels_to_source_host, on the GPU)."""
+def labels_at_source(handle, like, interpolate=False):
+    """The labels of `handle` at the source frames' size: numpy n x h x w uint8 (utils.image.labels_to_source_host, on the GPU).
+    interpolate=True: `handle` is the LOGITS handle of the frame; its scores are interpolated bilinearly to the source size and the
+    argmax is taken there (utils.image.labels_interpolated_host, on the GPU)."""
+    if interpolate:
+        m = _model(handle, "logits")
+        n, out_h, out_w, h, w = _geometry(handle, like, scores=True)
+        return m.scores_labels(n, out_h, out_w, h, w)
     m = _model(handle)
     n, out_h, out_w, h, w = _geometry(handle, like)
     return m.labels_to_source(n, out_h, out_w, h, w)
 
 
-def colour(handle, like, palette, frames=None, alpha=256, rgb=True):
+def colour(handle, like, palette, frames=None, alpha=256, rgb=True, interpolate=False):
     """The labels of `handle` as a colour image at the source frames' size: numpy n x h x w x 3 uint8, palette[label] (256 x 3 R, G, B)
     in R, G, B order (rgb=True) or B, G, R; blended over `frames` (uint8 n x h x w x 3 BGR; frames=True takes those of a RawFrames
-    `like`) with weight alpha / 256 (utils.image.colour_host, on the GPU)."""
-    m = _model(handle)
-    n, out_h, out_w, h, w = _geometry(handle, like)
+    `like`) with weight alpha / 256 (utils.image.colour_host, on the GPU).  interpolate=True: `handle` is the LOGITS handle and the
+    labels are those of labels_at_source(handle, like, interpolate=True)."""
+    m = _model(handle, "logits" if interpolate else "labels")
+    n, out_h, out_w, h, w = _geometry(handle, like, scores=bool(interpolate))
     if frames is True:
         frames = like.frames
+    if interpolate:
+        return m.scores_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
     return m.labels_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
 
 
@@ -120,9 +130,10 @@ class Evaluator(object):
         self._m = None
         self._base = np.zeros((self.num_classes, self.num_classes), np.int64)
 
-    def add(self, handle, gt, like=None):
-        """count `handle`'s labels against ground truth `gt` ([n x] h x w uint8; ids >= num_classes, such as 255, are ignored)"""
-        m = _model(handle)
+    def add(self, handle, gt, like=None, interpolate=False):
+        """count `handle`'s labels against ground truth `gt` ([n x] h x w uint8; ids >= num_classes, such as 255, are ignored).
+        interpolate=True: `handle` is the LOGITS handle and the labels are those of labels_at_source(handle, like, interpolate=True)"""
+        m = _model(handle, "logits" if interpolate else "labels")
         if self._m is None:
             self._base = m.hist_read(self.num_classes).astype(np.int64)
             self._m = m
@@ -133,10 +144,13 @@ class Evaluator(object):
             g = g[None]
         if g.dtype != np.uint8:
             g = np.where((g >= 0) & (g < 256), g, 255).astype(np.uint8)      # anything outside a byte is ignored either way
-        n, out_h, out_w, h, w = _geometry(handle, like, hw=g.shape[1:3])
+        n, out_h, out_w, h, w = _geometry(handle, like, hw=g.shape[1:3], scores=bool(interpolate))
         if g.shape[0] != n:
             raise ValueError("%d label maps but %d ground-truth maps" % (n, g.shape[0]))
-        m.hist_add(g, out_h, out_w, self.num_classes)
+        if interpolate:
+            m.scores_hist_add(g, out_h, out_w, self.num_classes)
+        else:
+            m.hist_add(g, out_h, out_w, self.num_classes)
 
     def hist(self, clear=False):
         """the confusion matrix so far: int64 num_classes x num_classes, rows ground truth, columns prediction (waits for the GPU)"""

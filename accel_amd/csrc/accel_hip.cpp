@@ -109,6 +109,10 @@ struct accel_model {
     size_t stage_out_bytes = 0;
     unsigned long long* hist = nullptr;
     int hist_ncls = 0;
+    // accel_model_scores_hist_add / _scores_colour: the labels of the interpolated scores at the source size (n x h x w uint8, tight rows)
+    // on their way to the counting / colouring kernel; grown on demand
+    unsigned char* interp_labels = nullptr;
+    size_t interp_labels_bytes = 0;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;
@@ -1662,6 +1666,7 @@ extern "C" int accel_model_destroy(accel_model* m)
     if (m->stage_u8) hipFree(m->stage_u8);
     if (m->stage_out) hipFree(m->stage_out);
     if (m->hist) hipFree(m->hist);
+    if (m->interp_labels) hipFree(m->interp_labels);
     delete m;
     return 0;
 }
@@ -2693,6 +2698,148 @@ extern "C" int accel_model_confidence(accel_model* m, int n, int out_h, int out_
     if (int rc = stage_out(m, cs.bytes, &base)) return rc;
     return confidence_to_host(fn, scores, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
                               hist, st);
+}
+
+// ---- labels from interpolated scores (scores_labels.hip) ------------------------------------------------------------------------------------
+// What the four entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int scores_labels_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w)
+{
+    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the scores must have 2, 19 or 21 classes", fn, ncls);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    return 0;
+}
+
+// the model's scores: the `logits` buffer and the shape the plans write it in
+static int model_scores(const char* fn, accel_model* m, int n, const float** scores, int* ncls, int* H, int* W)
+{
+    auto it = m->pbufs.find("logits");
+    if (it == m->pbufs.end() || m->logits_h < 1 || m->logits_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: this model has no `logits` buffer of a known shape (no plan with a score_tail op is bound)", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    *ncls = m->logits_ncls; *H = m->logits_h; *W = m->logits_w;
+    if (n > m->logits_n || (size_t)n * *ncls * *H * *W * sizeof(float) > it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %d", fn, n, m->logits_n);
+    *scores = static_cast<const float*>(it->second.ptr);
+    return 0;
+}
+
+// the model's scratch for n x h x w interpolated labels
+static int interp_scratch(accel_model* m, size_t bytes, unsigned char** dev)
+{
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (m->interp_labels_bytes < bytes) {
+        // (hipFree waits for the device: no kernel is still reading the old scratch)
+        if (m->interp_labels) { HIP_TRY(hipFree(m->interp_labels)); m->interp_labels = nullptr; m->interp_labels_bytes = 0; }
+        HIP_TRY(hipMalloc((void**)&m->interp_labels, bytes));
+        m->interp_labels_bytes = bytes;
+    }
+    *dev = m->interp_labels;
+    return 0;
+}
+
+extern "C" int accel_scores_labels(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                                   uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_scores_labels";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_scores_labels(s, n, ncls, H, W, out_h, out_w, h, w, d, (size_t)w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_model_scores_labels(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_scores_labels";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        HIP_TRY(launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, dst, dst_pitch, st));
+        return 0;
+    }
+    unsigned char* d = nullptr;
+    if (int rc = stage_out(m, (size_t)n * h * w, &d)) return rc;
+    HIP_TRY(launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, d, (size_t)w, st));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_scores_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                           int gt_on_device)
+{
+    const char* fn = "accel_model_scores_hist_add";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    const float* scores = nullptr;
+    int sncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &sncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, sncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (m->hist_ncls && m->hist_ncls != ncls)
+        return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the accumulator holds counts of %d classes since its last clear", fn, ncls, m->hist_ncls);
+    hipStream_t st = m->ctx->stream;
+    unsigned char* lab = nullptr;
+    if (int rc = interp_scratch(m, (size_t)n * h * w, &lab)) return rc;
+    if (!m->hist) {
+        HIP_TRY(hipMalloc((void**)&m->hist, 32 * 32 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(m->hist, 0, 32 * 32 * sizeof(unsigned long long), st));
+    }
+    const unsigned char* g = gt;
+    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
+    HIP_TRY(launch_scores_labels(scores, n, sncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
+    HIP_TRY(launch_labels_hist(lab, n, h, w, h, w, g, h, w, gt_pitch, ncls, m->hist, st));       // the scratch at the identity geometry
+    m->hist_ncls = ncls;
+    return 0;
+}
+
+extern "C" int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_scores_colour";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    hipStream_t st = m->ctx->stream;
+    unsigned char* lab = nullptr;
+    if (int rc = interp_scratch(m, (size_t)n * h * w, &lab)) return rc;
+    const unsigned char* f = frame_bgr;
+    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
+    unsigned char* d = dst;
+    if (!dst_on_device) if (int rc = stage_out(m, (size_t)n * h * w * 3, &d)) return rc;
+    HIP_TRY(launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
+    // the scratch at the identity geometry
+    HIP_TRY(launch_labels_colour(lab, n, h, w, h, w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, dst_on_device ? dst_pitch : (size_t)3 * w, st));
+    if (dst_on_device) return 0;
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)3 * w, (size_t)n * h, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
 }
 
 extern "C" int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes)

@@ -179,6 +179,11 @@ hipError_t launch_labels_colour(const unsigned char* labels, int n, int H, int W
 hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob, unsigned char* conf,
                              size_t conf_pitch, float* margin, size_t margin_pitch, unsigned char* second, size_t second_pitch, unsigned long long* hist,
                              hipStream_t st);
+// labels from interpolated scores (scores_labels.hip): the same scores and geometry vocabulary -> per source pixel the first-max argmax of the
+// ncls planes interpolated bilinearly (half-pixel centres, taps clamped to the valid region, float64 blend: utils/image.py
+// labels_interpolated_host), n x h x w uint8 with rows dst_pitch bytes apart.  Device pointers; the kernel only reads `scores`
+hipError_t launch_scores_labels(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,
+                                hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

@@ -197,6 +197,9 @@ def main(argv=None):
                     help='with --finish-on-gpu: per frame, the mean confidence (largest softmax probability) and the share of pixels '
                          'below level 128 of 256, from a histogram made on the GPU where the logits are; --out also writes '
                          'conf_<frame>.png in greyscale')
+    ap.add_argument('--interpolate', action='store_true',
+                    help='with --finish-on-gpu: the labels at the source size are the argmax of the bilinearly INTERPOLATED scores '
+                         '(made on the GPU where the logits are) instead of the nearest label of the finished map; the mIoU counts them')
     ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
                                                  '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
@@ -209,6 +212,8 @@ def main(argv=None):
         raise ValueError("Invalid num_ex %d - must be >=1" % num_ex)
     if args.confidence and not args.finish_on_gpu:
         raise ValueError("--confidence needs --finish-on-gpu")
+    if args.interpolate and not args.finish_on_gpu:
+        raise ValueError("--interpolate needs --finish-on-gpu")
     if args.nv12:
         args.raw_frames = True
     if args.cfg:
@@ -274,7 +279,7 @@ def main(argv=None):
         if idx + 1 < len(data) and not args.pageable:
             runner.prefetch(data[idx + 1])        # next frame starts crossing PCIe while this one computes
         if args.finish_on_gpu:
-            pred = results.labels_at_source(lab, source)[0]
+            pred = (results.labels_at_source(lg, source, interpolate=True) if args.interpolate else results.labels_at_source(lab, source))[0]
         else:
             pred = np.uint8(np.squeeze(lab.asnumpy()))
         elapsed = toc()
@@ -301,7 +306,10 @@ def main(argv=None):
             from PIL import Image
             label = np.asarray(Image.open(lf))
             if args.finish_on_gpu:      # counted on the GPU against `lab` itself; this frame's matrix is the difference of two reads
-                evaluator.add(lab, label, like=source)
+                if args.interpolate:
+                    evaluator.add(lg, label, like=source, interpolate=True)
+                else:
+                    evaluator.add(lab, label, like=source)
                 hist = evaluator.hist()
                 curr_hist, hist_before = hist - hist_before, hist
             else:

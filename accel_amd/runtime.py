@@ -91,6 +91,10 @@ def _declare(lib):
         "accel_model_labels_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
         "accel_scores_confidence": [vp, vp, i, i, i, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp],
         "accel_model_confidence": [vp, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp, i],
+        "accel_scores_labels": [vp, vp, i, i, i, i, i, i, i, i, vp, sz],
+        "accel_model_scores_labels": [vp, i, i, i, i, i, vp, sz, i],
+        "accel_model_scores_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
+        "accel_model_scores_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
         "accel_comm_available": [],
         "accel_comm_unique_id": [vp],
         "accel_comm_create": [vp, i, i, vp, c.POINTER(vp)],
@@ -439,6 +443,18 @@ class Context(object):
                                             p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], hp))
         return tuple(outs)
 
+    def scores_labels(self, scores, out_h, out_w, h, w, out=None):
+        """accel_scores_labels: n x ncls x H x W scores whose valid region is out_h x out_w -> n x h x w labels at the source size, the
+        argmax of the bilinearly interpolated scores (utils.image.labels_interpolated_host); `out`: n x h x pitch bytes to write the
+        rows into instead"""
+        a = _f32(scores)
+        if a.ndim != 4:
+            raise ValueError("scores must be n x ncls x H x W fp32, got shape %s" % (a.shape,))
+        n, ncls, H, W = a.shape
+        out, pitch = _result_rows(out, n, int(h), int(w), 1)
+        check(lib().accel_scores_labels(self.handle, _fp(a), n, ncls, H, W, int(out_h), int(out_w), int(h), int(w), _fp(out), pitch))
+        return out
+
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
         _, _, H, W = cur.shape
@@ -770,6 +786,35 @@ class Model(object):
         check(lib().accel_model_confidence(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
                                            vp(conf_ptr), int(conf_pitch), vp(margin_ptr), int(margin_pitch), vp(second_ptr), int(second_pitch),
                                            vp(hist_ptr), 1))
+
+    # ---- labels from interpolated scores: they only READ `logits` ------------------------------------------------------------
+    def scores_labels(self, n, out_h, out_w, h, w, out=None):
+        """accel_model_scores_labels: the argmax of the first n frames of `logits` interpolated to the source size h x w, as a numpy
+        n x h x w uint8 (utils.image.labels_interpolated_host)"""
+        out, pitch = _result_rows(out, int(n), int(h), int(w), 1)
+        check(lib().accel_model_scores_labels(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(out), pitch, 0))
+        return out
+
+    def scores_labels_device(self, dev_ptr, n, out_h, out_w, h, w, pitch):
+        """the same into caller-owned HBM (enqueued, no host wait)"""
+        check(lib().accel_model_scores_labels(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), ctypes.c_void_p(dev_ptr), int(pitch), 1))
+
+    def scores_hist_add(self, gt, out_h, out_w, ncls, width=None):
+        """accel_model_scores_hist_add: hist_add with the labels of the interpolated scores: the same accumulator, the same ncls rule"""
+        g, n, h, w, pitch = _u8_maps(gt, width, "gt")
+        check(lib().accel_model_scores_hist_add(self.handle, _fp(g), n, h, w, pitch, int(out_h), int(out_w), int(ncls), 0))
+
+    def scores_colour(self, n, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
+        """accel_model_scores_colour: labels_colour with the labels of the interpolated scores"""
+        f, fp = None, 0
+        if frames is not None:
+            f, fn, fh, fw, fp = _u8_frames(frames, width)
+            if (fn, fh, fw) != (int(n), int(h), int(w)):
+                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn, fh, fw, n, h, w))
+        out, pitch = _result_rows(out, int(n), int(h), int(w), 3)
+        check(lib().accel_model_scores_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
+                                              None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
+        return out
 
     def read_async(self, buf, pinned):
         """enqueue the download of `buf` into a PinnedBuffer on the compute stream; valid after ctx.sync()"""

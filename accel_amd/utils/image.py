@@ -141,6 +141,53 @@ def confidence_host(scores, out_h, out_w, h, w, is_prob=False):
     return conf, margin, second.astype(np.uint8), hist
 
 
+def interpolation_taps(dst, src):
+    """(i0, i1, f): the two rows (or columns) of a `src`-pixel region that each of `dst` output rows blends under bilinear resizing
+    with half-pixel centres, and the float64 weight of the second.  The coordinate (i + 0.5) * src / dst - 0.5 clamped to the region,
+    in integer arithmetic with ONE division in float64 -- the inverse of the resize `_resize_bilinear` applies on the way in, and the
+    form csrc/scores_labels.hip computes (every intermediate is below 2^31 for sizes up to 32768)."""
+    dst, src = int(dst), int(src)
+    num = np.clip((2 * np.arange(dst, dtype=np.int64) + 1) * src - dst, 0, 2 * dst * (src - 1))
+    i0 = num // (2 * dst)
+    i1 = np.minimum(i0 + 1, src - 1)
+    f = (num - 2 * dst * i0).astype(np.float64) / np.float64(2 * dst)
+    return i0, i1, f
+
+
+def labels_interpolated_host(scores, out_h, out_w, h, w):
+    """The specification of accel_scores_labels: scores n x ncls x H x W fp32 (valid region out_h x out_w in the top-left corner) ->
+    labels n x h x w uint8 at the source size: every class plane interpolated bilinearly to the source pixel (interpolation_taps; the
+    padding is never read), the argmax taken there.  The blend is float64 with every operation rounded on its own, in the order of
+    `_resize_bilinear`: top = a00 * (1 - fx) + a01 * fx, bot = a10 * (1 - fx) + a11 * fx, v = top * (1 - fy) + bot * fy.  The label
+    is the first class with the largest v (ascending scan, strict >: np.argmax).  At h x w == out_h x out_w every weight is 0 and v
+    is the stored score: the crop of the argmax.  Scores are assumed finite."""
+    s = np.asarray(scores, np.float32)
+    if s.ndim != 4:
+        raise ValueError("scores must be n x ncls x H x W, got shape %s" % (s.shape,))
+    n, ncls = s.shape[:2]
+    if not (1 <= int(out_h) <= s.shape[2] and 1 <= int(out_w) <= s.shape[3]):
+        raise ValueError("the valid region %d x %d does not lie in the %d x %d map" % (out_h, out_w, s.shape[2], s.shape[3]))
+    y0, y1, fy = interpolation_taps(h, out_h)
+    x0, x1, fx = interpolation_taps(w, out_w)
+    fy, fx = fy[None, :, None], fx[None, None, :]
+    gy, gx = 1 - fy, 1 - fx
+    best = None
+    label =np.zeros((n, int(h), int(w)), np.uint8)
+    for k in range(ncls):
+        a = s[:, k, :int(out_h), :int(out_w)].astype(np.float64)
+        r0, r1 = a[:, y0], a[:, y1]
+        top = r0[:, :, x0] * gx + r0[:, :, x1] * fx
+        bot = r1[:, :, x0] * gx + r1[:, :, x1] * fx
+        v = top * gy + bot * fy
+        if k == 0:
+            best = v
+        else:
+            better = v > best
+            best = np.where(better, v, best)
+            label[better] = k
+    return label
+
+
 def transform(im, pixel_means):
     """Contract of lib/utils/image.py:224-235: a BGR H x W x 3 frame becomes the 1 x 3 x H x W RGB tensor with the per-channel
     mean removed (`pixel_means` is given in B, G, R order like the frame).  float64 like the reference; arrays become fp32

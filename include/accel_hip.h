@@ -321,6 +321,45 @@ int accel_scores_confidence(accel_ctx* ctx, const float* scores, int n, int ncls
 int accel_model_confidence(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch,
                            float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist, int dst_on_device);
 
+/* ---- finished frames: labels from interpolated scores ---------------------------------------------------------------
+ * Labels at the source frame's size the way segmentation is usually evaluated: every class plane of the scores is
+ * interpolated bilinearly to the source pixel and the argmax is taken THERE (csrc/scores_labels.hip), instead of copying
+ * the finished label of the nearest map pixel (accel_labels_to_source) -- and instead of `logits.asnumpy()` plus a blend
+ * of ncls planes on the host.  `scores` is n x ncls x H x W fp32 (NCHW, the layout of `logits`), ncls in {2, 19, 21}; the
+ * geometry vocabulary is that of the blocks above (valid region out_h x out_w, source size h x w).  The specification is
+ * accel_amd/utils/image.py labels_interpolated_host; the kernel restates it bit for bit.
+ *   taps     in integer arithmetic, for source row y of h rows over a region of out_h rows (columns alike with w, out_w):
+ *                num = clamp((2 * y + 1) * out_h - h, 0, 2 * h * (out_h - 1))           (< 2^31: sizes are <= 32768)
+ *                y0 = num / (2 * h),  y1 = min(y0 + 1, out_h - 1),  fy = double(num - 2 * h * y0) / double(2 * h)
+ *            (ONE IEEE division): the half-pixel-centre coordinate (y + 0.5) * out_h / h - 0.5 clamped to the region, the
+ *            inverse of the resize of the input side.  Taps never leave the valid region: the padding is never read
+ *   blend    in float64, each operation rounded on its own (no fma), a<row><col> the four fp32 taps as doubles:
+ *                gx = 1 - fx, gy = 1 - fy, top = a00 * gx + a01 * fx, bot = a10 * gx + a11 * fx, v_k = top * gy + bot * fy
+ *   label    the first k with the largest v_k (ascending scan, strict >): the tie rule of `labels`
+ * At h x w == out_h x out_w, fx = fy = 0 and v_k is the stored score: the result is the crop of `labels`, which is what
+ * accel_labels_to_source gives there.  Scores are assumed FINITE: a pixel with a non-finite tap is unspecified (inf * 0
+ * arises in the blend).  Rows of dst are `dst_pitch` bytes apart; bytes between rows are not written.
+ * Argument errors (a NULL pointer, a size < 1 or > 32768, out_h > H, out_w > W, a pitch smaller than a row, an unsupported
+ * ncls, n larger than the bound batch, no `logits` buffer, and for _hist_add / _colour those of their label forms) return
+ * ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_scores_labels         operator level: host scores in, host labels out (the parity tests)
+ *   accel_model_scores_labels, accel_model_scores_hist_add, accel_model_scores_colour
+ *                               on the model's `logits` buffer (n, ncls, H, W as the bound plans write it), enqueued on the
+ *                               context stream after the run that wrote it.  They only read `logits`: no write generation
+ *                               changes, no captured graph is touched.  _hist_add and _colour write the interpolated labels
+ *                               into a model-owned n x h x w scratch (grown on demand, freed with the model) and then run
+ *                               the kernels of accel_model_hist_add / accel_model_labels_colour on it at the identity
+ *                               geometry: _hist_add adds into the SAME accumulator under the same ncls rule (its `ncls` is
+ *                               the evaluation's class count, 1 .. 32; the class count of the scores is that of `logits`);
+ *                               *_on_device as in the label forms */
+int accel_scores_labels(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                        uint8_t* dst, size_t dst_pitch);
+int accel_model_scores_labels(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device);
+int accel_model_scores_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device);
+int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                              const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                              uint8_t* dst, size_t dst_pitch, int dst_on_device);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
