@@ -1,0 +1,846 @@
+// libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
+// points behind them -- uint8 and NV12 frames in, finished frames, confidence and interpolated labels out (see include/accel_hip.h).  Nothing
+// here knows about plans.
+#include <cstring>
+
+#include "accel_objects.h"
+#include "kernels.h"
+
+// a write into the model's own buffer ends a binding made by accel_model_bind_device
+static int unbind(accel_model* m, DevBuf& b)
+{
+    if (!b.bound) return 0;
+    HIP_TRY(launch_set_slot(b.slot, b.ptr, m->ctx->stream));
+    b.bound = nullptr;
+    return 0;
+}
+
+extern "C" int accel_model_bind_device(accel_model* m, const char* buf, const void* devptr, size_t bytes)
+{
+    if (!m || !buf || !devptr) return fail(ACCEL_ERR_ARG, "accel_model_bind_device: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_bind_device: unknown buffer '%s'", buf);
+    DevBuf& b = it->second;
+    if (!b.slot || b.readers != b.prep_readers)
+        return fail(ACCEL_ERR_ARG, "accel_model_bind_device: '%s' is not an image input of the finalized plans (only buffers that prep_rgb / "
+                                   "prep_flow alone read can be bound)", buf);
+    if (bytes != b.bytes) return fail(ACCEL_ERR_ARG, "accel_model_bind_device: %zu bytes, buffer '%s' has %zu", bytes, buf, b.bytes);
+    if (b.bound != devptr) HIP_TRY(launch_set_slot(b.slot, devptr, m->ctx->stream));
+    b.bound = devptr == b.ptr ? nullptr : devptr;
+    m->source_written(buf);
+    return 0;
+}
+
+extern "C" int accel_model_write(accel_model* m, const char* buf, const void* src, size_t bytes, int src_on_device)
+{
+    if (!m || !buf || !src) return fail(ACCEL_ERR_ARG, "accel_model_write: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_write: unknown buffer '%s'", buf);
+    if (bytes > it->second.bytes) return fail(ACCEL_ERR_ARG, "accel_model_write: %zu bytes > buffer '%s' (%zu)", bytes, buf, it->second.bytes);
+    if (int rc = unbind(m, it->second)) return rc;
+    if (src_on_device) HIP_TRY(launch_copy_bytes(src, it->second.ptr, bytes, m->ctx->stream));      // own copy kernel: 4x the rate of the runtime's blit
+    else HIP_TRY(hipMemcpyAsync(it->second.ptr, src, bytes, hipMemcpyHostToDevice, m->ctx->stream));
+    if (!src_on_device) HIP_TRY(hipStreamSynchronize(m->ctx->stream));   // pageable source may be reused by the caller
+    m->source_written(buf);
+    return 0;
+}
+
+extern "C" int accel_model_read(accel_model* m, const char* buf, void* dst, size_t bytes, int dst_on_device)
+{
+    if (!m || !buf || !dst) return fail(ACCEL_ERR_ARG, "accel_model_read: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_read: unknown buffer '%s'", buf);
+    if (bytes > it->second.bytes) return fail(ACCEL_ERR_ARG, "accel_model_read: %zu bytes > buffer '%s' (%zu)", bytes, buf, it->second.bytes);
+    // a bound input is read where the plans read it (the caller's frame), not the model-owned copy an earlier write left behind
+    const void* src = it->second.bound ? it->second.bound : it->second.ptr;
+    if (dst_on_device) HIP_TRY(launch_copy_bytes(src, dst, bytes, m->ctx->stream));
+    else HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->ctx->stream));
+    if (!dst_on_device) HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_model_buffer(accel_model* m, const char* buf, void** dev_ptr, size_t* bytes)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_buffer: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_buffer: unknown buffer '%s'", buf);
+    // the caller is about to write the model-owned buffer through the raw pointer: a binding made by accel_model_bind_device
+    // ends here (the plans read the model's copy again), otherwise that write would be silently ignored
+    if (dev_ptr) if (int rc = unbind(m, it->second)) return rc;
+    if (dev_ptr) *dev_ptr = it->second.ptr;
+    if (bytes) *bytes = it->second.bytes;
+    if (dev_ptr) m->source_written(buf);   // the caller may write through the raw pointer: derived buffers become stale
+    return 0;
+}
+
+extern "C" int accel_model_buffer_generation(accel_model* m, const char* buf, uint64_t* generation)
+{
+    if (!m || !buf || !generation) return fail(ACCEL_ERR_ARG, "accel_model_buffer_generation: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_buffer_generation: unknown buffer '%s'", buf);
+    auto it = m->generation.find(buf);
+    *generation = it == m->generation.end() ? 0 : it->second;
+    return 0;
+}
+
+extern "C" int accel_host_alloc(size_t bytes, void** out)
+{
+    if (!out || !bytes) return fail(ACCEL_ERR_ARG, "accel_host_alloc: bad argument");
+    HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocDefault));
+    return 0;
+}
+
+extern "C" int accel_host_free(void* p)
+{
+    if (p) HIP_TRY(hipHostFree(p));
+    return 0;
+}
+
+// ---- prefetch and commit: what the fp32 route and the uint8 route (BGR and NV12 bytes) share ------------------------------------------------
+typedef accel_model::Shadow Shadow;
+
+// `bytes` from pinned memory into a shadow of at least `reserve` bytes, on the copy stream
+static int prefetch_into(accel_model* m, Shadow& sh, size_t reserve, const void* pinned_src, size_t bytes)
+{
+    const bool grows = sh.mem.bytes < reserve;      // (hipFree waits for the device, so for whoever read the old shadow)
+    if (int rc = sh.mem.reserve(m->ctx->device, reserve)) return rc;
+    if (!sh.ready) {
+        HIP_TRY(hipEventCreateWithFlags(&sh.ready, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&sh.consumed, hipEventDisableTiming));
+    }
+    // the previous commit read the shadow on the compute stream (event recorded right behind that copy or kernel, ahead of the
+    // plan that followed): do not overwrite under it -- and wait for nothing else on that stream
+    if (!grows && sh.was_consumed) HIP_TRY(hipStreamWaitEvent(m->ctx->copy, sh.consumed, 0));
+    HIP_TRY(hipMemcpyAsync(sh.mem.ptr, pinned_src, bytes, hipMemcpyHostToDevice, m->ctx->copy));
+    HIP_TRY(hipEventRecord(sh.ready, m->ctx->copy));
+    sh.filled = bytes;
+    return 0;
+}
+
+// the shadow of `buf` if a prefetch is waiting in it
+static Shadow* prefetched(std::map<std::string, Shadow>& shadows, const char* buf)
+{
+    auto it = shadows.find(buf);
+    return it == shadows.end() || !it->second.filled ? nullptr : &it->second;
+}
+
+// the compute stream waits for the prefetch, `launch(src, dst, stream)` moves the shadow into the model-owned buffer, the shadow is free again
+template <class Launch>
+static int commit_from(accel_model* m, const char* buf, DevBuf& b, Shadow& sh, Launch launch)
+{
+    HIP_TRY(hipStreamWaitEvent(m->ctx->stream, sh.ready, 0));
+    if (int rc = unbind(m, b)) return rc;
+    HIP_TRY(launch(sh.mem.ptr, b.ptr, m->ctx->stream));
+    HIP_TRY(hipEventRecord(sh.consumed, m->ctx->stream));
+    sh.was_consumed = true;
+    sh.filled = 0;
+    m->source_written(buf);
+    return 0;
+}
+
+// host bytes on their way to a kernel (frames, ground truth, a frame to blend with): through the staging buffer, on the compute stream
+static int stage_in(accel_model* m, const void* host, size_t bytes, const unsigned char** dev)
+{
+    if (int rc = m->stage_u8.reserve(m->ctx->device, bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(m->stage_u8.ptr, host, bytes, hipMemcpyHostToDevice, m->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));   // pageable source may be reused by the caller
+    *dev = m->stage_u8.ptr;
+    return 0;
+}
+
+extern "C" int accel_model_prefetch(accel_model* m, const char* buf, const void* pinned_src, size_t bytes)
+{
+    if (!m || !buf || !pinned_src) return fail(ACCEL_ERR_ARG, "accel_model_prefetch: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_prefetch: unknown buffer '%s'", buf);
+    if (bytes > it->second.bytes) return fail(ACCEL_ERR_ARG, "accel_model_prefetch: %zu bytes > buffer '%s' (%zu)", bytes, buf, it->second.bytes);
+    return prefetch_into(m, m->shadows[buf], it->second.bytes, pinned_src, bytes);       // sized to the whole buffer on first use
+}
+
+extern "C" int accel_model_commit(accel_model* m, const char* buf)
+{
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit: NULL argument");
+    Shadow* sh = prefetched(m->shadows, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit: nothing was prefetched for '%s'", buf);
+    return commit_from(m, buf, m->pbufs[buf], *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
+        return launch_copy_bytes(src, dst, sh->filled, st);
+    });
+}
+
+// device temporaries of the operator-level entry points
+struct DevTemps {
+    std::vector<void*> ptrs;
+    ~DevTemps() { for (void* p : ptrs) hipFree(p); }
+    void* get(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr; ptrs.push_back(p); return p; }
+    void* upload(const void* host, size_t bytes) { void* p = get(bytes); if (p && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
+};
+
+// ---- uint8 frames ---------------------------------------------------------------------------------------------------------------
+// The resize a frame conversion is told (out_h, out_w, step) and the padded size H x W, for an h x w source: shared by the BGR and the NV12 route.
+static int frame_resize_args(const char* fn, int h, int w, int out_h, int out_w, double step, int H, int W)
+{
+    if (!(step > 0.0) || step > 1e9) return fail(ACCEL_ERR_ARG, "%s: step = %g, must be a positive number of source pixels per output pixel", fn, step);
+    if (H < 1 || W < 1) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be >= 1", fn, H, W);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    if (step == 1.0 && (out_h != h || out_w != w))
+        return fail(ACCEL_ERR_ARG, "%s: step = 1 copies the frame, but out_h x out_w = %d x %d is not h x w = %d x %d", fn, out_h, out_w, h, w);
+    return 0;
+}
+
+// Geometry of a uint8 frame conversion, checked before anything is enqueued: every message names the argument at fault.
+static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
+                         int H, int W)
+{
+    if (!bgr) return fail(ACCEL_ERR_ARG, "%s: bgr is NULL", fn);
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (h < 1) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be >= 1", fn, h);
+    if (w < 1) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be >= 1", fn, w);
+    if (pitch < (size_t)3 * w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %zu", fn, pitch, w, (size_t)3 * w);
+    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
+}
+
+static int frame_u8_buf(const char* fn, accel_model* m, const char* buf, int n, int H, int W, DevBuf** out)
+{
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "%s: unknown buffer '%s'", fn, buf);
+    const size_t need = (size_t)n * 3 * H * W * 4;
+    if (need != it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n x 3 x H x W fp32 = %d x 3 x %d x %d = %zu bytes, buffer '%s' has %zu", fn, n, H, W, need, buf, it->second.bytes);
+    *out = &it->second;
+    return 0;
+}
+
+extern "C" int accel_frame_u8(accel_ctx* ctx, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                              int out_h, int out_w, double step, int H, int W, float* out)
+{
+    const char* fn = "accel_frame_u8";
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_u8: NULL argument");
+    if (int rc = frame_u8_args(fn, bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ob = (size_t)n * 3 * H * W * 4;
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(bgr, (size_t)n * h * pitch));
+    float* d = static_cast<float*>(t.get(ob));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_frames_u8(s, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Frames of `src_bytes` bytes, converted by `launch(src, dst, stream)` into the image input `buf` of n x 3 x H x W fp32: what the BGR and the NV12
+// route share once their own arguments are checked.  A host source goes through the staging buffer.
+template <class Launch>
+static int write_frames(const char* fn, accel_model* m, const char* buf, int n, int H, int W, const unsigned char* src, size_t src_bytes,
+                        int src_on_device, Launch launch)
+{
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    if (!src_on_device) if (int rc = stage_in(m, src, src_bytes, &src)) return rc;
+    if (int rc = unbind(m, *b)) return rc;
+    HIP_TRY(launch(src, static_cast<float*>(b->ptr), m->ctx->stream));
+    m->source_written(buf);
+    return 0;
+}
+
+extern "C" int accel_model_write_u8(accel_model* m, const char* buf, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                                    int out_h, int out_w, double step, int H, int W, int src_on_device)
+{
+    const char* fn = "accel_model_write_u8";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_u8: NULL argument");
+    if (int rc = frame_u8_args(fn, bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return write_frames(fn, m, buf, n, H, W, bgr, (size_t)n * h * pitch, src_on_device, [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, dst, st);
+    });
+}
+
+extern "C" int accel_model_prefetch_u8(accel_model* m, const char* buf, const void* pinned_src, size_t bytes)
+{
+    if (!m || !buf || !pinned_src) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: unknown buffer '%s'", buf);
+    if (!bytes) return fail(ACCEL_ERR_ARG, "accel_model_prefetch_u8: bytes = 0");
+    return prefetch_into(m, m->shadows_u8[buf], bytes, pinned_src, bytes);       // frames of another size: the shadow grows to the bytes asked for
+}
+
+extern "C" int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, const double* means_bgr,
+                                     int out_h, int out_w, double step, int H, int W)
+{
+    const char* fn = "accel_model_commit_u8";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: unknown buffer '%s'", buf);
+    Shadow* sh = prefetched(m->shadows_u8, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_u8_args(fn, sh->mem.ptr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    if ((size_t)n * h * pitch > sh->filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: n x h x pitch = %d x %d x %zu bytes, %zu were prefetched for '%s'", n, h, pitch, sh->filled, buf);
+    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
+        return launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
+    });
+}
+
+// ---- NV12 frames (frames_nv12.hip) ------------------------------------------------------------------------------------------------
+extern "C" int accel_nv12_coefficients(int colour, int32_t out[6])
+{
+    if (!out) return fail(ACCEL_ERR_ARG, "accel_nv12_coefficients: out is NULL");
+    const int32_t* c = nv12_coefficients(colour);
+    if (!c) return fail(ACCEL_ERR_ARG, "accel_nv12_coefficients: colour = %d, must be in 0 .. 3", colour);
+    for (int i = 0; i < 6; ++i) out[i] = c[i];
+    return 0;
+}
+
+// Layout of NV12 frames, checked before anything is enqueued: every message names the argument at fault.
+static int nv12_layout_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour)
+{
+    const int lim = 32768;
+    if (!nv12) return fail(ACCEL_ERR_ARG, "%s: nv12 is NULL", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (h < 2 || h > lim || h % 2) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be even and in 2 .. %d", fn, h, lim);
+    if (w < 2 || w > lim || w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 2 .. %d", fn, w, lim);
+    if (pitch < (size_t)w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %d", fn, pitch, w, w);
+    if (pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, pitch);
+    if (uv_offset < (size_t)h * pitch)
+        return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, uv_offset, h, pitch, (size_t)h * pitch);
+    if (uv_offset > ((size_t)1 << 60)) return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes is not an offset into a frame", fn, uv_offset);
+    if (frame_bytes < uv_offset + (size_t)(h / 2) * pitch)
+        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the chroma plane at uv_offset = %zu ends at %zu", fn, frame_bytes, uv_offset,
+                    uv_offset + (size_t)(h / 2) * pitch);
+    if (frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, frame_bytes);
+    if (colour < 0 || colour > 3) return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, colour);
+    return 0;
+}
+
+static int frame_nv12_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                           const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    if (int rc = nv12_layout_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
+}
+
+// the bytes n frames occupy: the last one ends with its chroma plane
+static size_t nv12_bytes(int n, int h, size_t pitch, size_t uv_offset, size_t frame_bytes)
+{
+    return (size_t)(n - 1) * frame_bytes + uv_offset + (size_t)(h / 2) * pitch;
+}
+
+extern "C" int accel_frame_nv12(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* out)
+{
+    const char* fn = "accel_frame_nv12";
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_nv12: NULL argument");
+    if (int rc = frame_nv12_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ob = (size_t)n * 3 * H * W * 4;
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes)));
+    float* d = static_cast<float*>(t.get(ob));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_frames_nv12(s, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_nv12_to_bgr(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                 uint8_t* bgr_out, size_t out_pitch, int on_device)
+{
+    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: NULL argument");
+    if (int rc = nv12_layout_args("accel_nv12_to_bgr", nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
+    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: bgr_out is NULL");
+    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
+        return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on_device) {
+        HIP_TRY(launch_nv12_to_bgr(nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, bgr_out, out_pitch, ctx->stream));
+        return 0;
+    }
+    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes)));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: device allocation or upload failed");
+    HIP_TRY(launch_nv12_to_bgr(s, n, h, w, pitch, uv_offset, frame_bytes, colour, d, (size_t)3 * w, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset,
+                                      size_t frame_bytes, int colour, const double* means_bgr, int out_h, int out_w, double step, int H, int W,
+                                      int src_on_device)
+{
+    const char* fn = "accel_model_write_nv12";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_nv12: NULL argument");
+    if (int rc = frame_nv12_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return write_frames(fn, m, buf, n, H, W, nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes), src_on_device,
+                        [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, dst, st);
+    });
+}
+
+// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow: bytes are bytes)
+extern "C" int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                       const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    const char* fn = "accel_model_commit_nv12";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: unknown buffer '%s'", buf);
+    Shadow* sh = prefetched(m->shadows_u8, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_nv12_args(fn, sh->mem.ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    const size_t need = nv12_bytes(n, h, pitch, uv_offset, frame_bytes);
+    if (need > sh->filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: (n - 1) x frame_bytes + uv_offset + h/2 x pitch = %zu bytes, %zu were prefetched for '%s'",
+                    need, sh->filled, buf);
+    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
+        return launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
+    });
+}
+
+// ---- finished frames: labels at the source size, confusion matrix, colour image (results_u8.hip) ---------------------------------------
+// Geometry shared by the three, checked before anything is enqueued: every message names the argument at fault.
+static int results_args(const char* fn, int n, int H, int W, int out_h, int out_w, int h, int w)
+{
+    const int lim = 32768;       // the kernels index with 32-bit products of two sizes
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (H < 1 || W < 1 || H > lim || W > lim) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be in 1 .. %d", fn, H, W, lim);
+    if (h < 1 || h > lim) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be in 1 .. %d", fn, h, lim);
+    if (w < 1 || w > lim) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be in 1 .. %d", fn, w, lim);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    return 0;
+}
+
+static int pitch_arg(const char* fn, const char* name, size_t pitch, int w, int bytes_per_pixel)
+{
+    if (pitch < (size_t)bytes_per_pixel * w)
+        return fail(ACCEL_ERR_ARG, "%s: %s = %zu bytes, a row of w = %d pixels has %zu", fn, name, pitch, w, (size_t)bytes_per_pixel * w);
+    return 0;
+}
+
+static int ncls_arg(const char* fn, int ncls)
+{
+    if (ncls < 1 || ncls > 32) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be in 1 .. 32", fn, ncls);
+    return 0;
+}
+
+static int alpha_arg(const char* fn, int alpha)
+{
+    if (alpha < 0 || alpha > 256) return fail(ACCEL_ERR_ARG, "%s: alpha = %d, must be in 0 .. 256", fn, alpha);
+    return 0;
+}
+
+// rows of `row` bytes, `pitch` apart on the host, tightly packed in device memory: only the bytes of the rows are written
+static hipError_t rows_to_host(void* dst, size_t pitch, const void* dev, size_t row, size_t rows, hipStream_t st)
+{
+    if (pitch == row) return hipMemcpyAsync(dst, dev, row * rows, hipMemcpyDeviceToHost, st);
+    return hipMemcpy2DAsync(dst, pitch, dev, row, row, rows, hipMemcpyDeviceToHost, st);
+}
+
+extern "C" int accel_labels_to_source(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                                      uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_labels_to_source";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w));
+    if (!l || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_source(l, n, H, W, out_h, out_w, h, w, d, (size_t)w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_labels_hist(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w,
+                                 const uint8_t* gt, int h, int w, size_t gt_pitch, int ncls, uint64_t* hist)
+{
+    const char* fn = "accel_labels_hist";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    if (!hist) return fail(ACCEL_ERR_ARG, "%s: hist is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const size_t hb = (size_t)ncls * ncls * sizeof(uint64_t);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* g = static_cast<const unsigned char*>(t.upload(gt, (size_t)n * h * gt_pitch));
+    unsigned long long* d = static_cast<unsigned long long*>(t.upload(hist, hb));
+    if (!l || !g || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_hist(l, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, d, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hist, d, hb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_labels_colour(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w,
+                                   const uint8_t* palette_rgb, int rgb_order, const uint8_t* frame_bgr, size_t frame_pitch, int alpha,
+                                   uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_labels_colour";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* f = frame_bgr ? static_cast<const unsigned char*>(t.upload(frame_bgr, (size_t)n * h * frame_pitch)) : nullptr;
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w * 3));
+    if (!l || !d || (frame_bgr && !f)) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_colour(l, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, (size_t)3 * w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)3 * w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// the model's label maps: the `labels` buffer and the shape the plans write it in
+static int model_labels(const char* fn, accel_model* m, int n, const unsigned char** labels)
+{
+    auto it = m->pbufs.find("labels");
+    if (it == m->pbufs.end() || m->labels_h < 1 || m->labels_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: this model has no `labels` buffer of a known shape (no plan with a score_tail op is bound)", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (n > m->labels_n || (size_t)n * m->labels_h * m->labels_w > it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %d", fn, n, m->labels_n);
+    *labels = static_cast<const unsigned char*>(it->second.ptr);
+    return 0;
+}
+
+// the model's scores: the `logits` buffer and the shape the plans write it in
+static int model_scores(const char* fn, accel_model* m, int n, const float** scores, int* ncls, int* H, int* W)
+{
+    auto it = m->pbufs.find("logits");
+    if (it == m->pbufs.end() || m->logits_h < 1 || m->logits_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: this model has no `logits` buffer of a known shape (no plan with a score_tail op is bound)", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    *ncls = m->logits_ncls; *H = m->logits_h; *W = m->logits_w;
+    if (n > m->logits_n || (size_t)n * *ncls * *H * *W * sizeof(float) > it->second.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %d", fn, n, m->logits_n);
+    *scores = static_cast<const float*>(it->second.ptr);
+    return 0;
+}
+
+// Where the `rows` rows of `row` bytes of a result go.  Into the caller's device memory at the caller's pitch: `launch(dst, pitch, stream)` is enqueued
+// and that is all.  To the host: the kernel writes tight rows into the staging buffer, they are copied `dst_pitch` apart, and the call waits.
+template <class Launch>
+static int result_rows(accel_model* m, uint8_t* dst, size_t dst_pitch, int dst_on_device, size_t row, size_t rows, Launch launch)
+{
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        HIP_TRY(launch(dst, dst_pitch, st));
+        return 0;
+    }
+    if (int rc = m->stage_out.reserve(m->ctx->device, row * rows)) return rc;
+    HIP_TRY(launch(m->stage_out.ptr, row, st));
+    HIP_TRY(rows_to_host(dst, dst_pitch, m->stage_out.ptr, row, rows, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the model's confusion matrix for counts of `ncls` classes: refused while it holds counts of another number of classes, allocated and zeroed on first use
+static int model_hist(const char* fn, accel_model* m, int ncls, unsigned long long** hist)
+{
+    if (m->hist_ncls && m->hist_ncls != ncls)
+        return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the accumulator holds counts of %d classes since its last clear", fn, ncls, m->hist_ncls);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (!m->hist) {
+        HIP_TRY(hipMalloc((void**)&m->hist, 32 * 32 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(m->hist, 0, 32 * 32 * sizeof(unsigned long long), m->ctx->stream));
+    }
+    *hist = m->hist;
+    return 0;
+}
+
+extern "C" int accel_model_labels_to_source(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_labels_to_source";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
+        return launch_labels_source(labels, n, H, W, out_h, out_w, h, w, d, pitch, st);
+    });
+}
+
+extern "C" int accel_model_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device)
+{
+    const char* fn = "accel_model_hist_add";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    unsigned long long* hist = nullptr;
+    if (int rc = model_hist(fn, m, ncls, &hist)) return rc;
+    const unsigned char* g = gt;
+    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
+    HIP_TRY(launch_labels_hist(labels, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, hist, m->ctx->stream));
+    m->hist_ncls = ncls;
+    return 0;
+}
+
+extern "C" int accel_model_hist_read(accel_model* m, uint64_t* out, int ncls, int clear)
+{
+    const char* fn = "accel_model_hist_read";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!out) return fail(ACCEL_ERR_ARG, "%s: out is NULL", fn);
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    const size_t hb = (size_t)ncls * ncls * sizeof(uint64_t);
+    if (!m->hist_ncls) { memset(out, 0, hb); return 0; }      // nothing added since the last clear: any class count may be asked for
+    unsigned long long* hist = nullptr;
+    if (int rc = model_hist(fn, m, ncls, &hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(out, hist, hb, hipMemcpyDeviceToHost, st));
+    if (clear) {
+        HIP_TRY(hipMemsetAsync(hist, 0, 32 * 32 * sizeof(unsigned long long), st));
+        m->hist_ncls = 0;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_labels_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_labels_colour";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    const unsigned char* f = frame_bgr;
+    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
+    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)3 * w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
+        return launch_labels_colour(labels, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);
+    });
+}
+
+// ---- confidence of finished frames (confidence.hip) ----------------------------------------------------------------------------------------
+// What the two entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int confidence_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, const void* conf, size_t conf_pitch,
+                           const void* margin, size_t margin_pitch, const void* second, size_t second_pitch, const void* hist)
+{
+    if (!conf && !margin && !second && !hist) return fail(ACCEL_ERR_ARG, "%s: conf, margin, second and hist are all NULL: nothing to compute", fn);
+    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be 2, 19 or 21", fn, ncls);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    if (conf) if (int rc = pitch_arg(fn, "conf_pitch", conf_pitch, w, 1)) return rc;
+    if (margin) {
+        if (int rc = pitch_arg(fn, "margin_pitch", margin_pitch, w, 4)) return rc;
+        if (margin_pitch % 4) return fail(ACCEL_ERR_ARG, "%s: margin_pitch = %zu bytes, must be a multiple of 4", fn, margin_pitch);
+    }
+    if (second) if (int rc = pitch_arg(fn, "second_pitch", second_pitch, w, 1)) return rc;
+    return 0;
+}
+
+// the device side of a call whose results go to the host: tight rows in `base` (conf, second: n * h * w bytes; margin: 4 times that; hist: n * 256
+// words), each part 256-byte aligned
+struct ConfStage {
+    size_t conf = 0, second = 0, margin = 0, hist = 0, bytes = 0;
+    ConfStage(int n, int h, int w, bool c, bool mg, bool s, bool hi)
+    {
+        const size_t px = (size_t)n * h * w;
+        auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
+        if (c) conf = take(px);
+        if (s) second = take(px);
+        if (mg) margin = take(px * 4);
+        if (hi) hist = take((size_t)n * 256 * sizeof(uint64_t));
+    }
+};
+
+static int confidence_to_host(const char* fn, const float* scores, unsigned char* base, const ConfStage& cs, int n, int ncls, int H, int W, int out_h, int out_w,
+                              int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second,
+                              size_t second_pitch, uint64_t* hist, hipStream_t st)
+{
+    unsigned char* dc = conf ? base + cs.conf : nullptr;
+    unsigned char* ds = second ? base + cs.second : nullptr;
+    float* dm = margin ? reinterpret_cast<float*>(base + cs.margin) : nullptr;
+    unsigned long long* dh = hist ? reinterpret_cast<unsigned long long*>(base + cs.hist) : nullptr;
+    HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
+    if (conf) HIP_TRY(rows_to_host(conf, conf_pitch, dc, (size_t)w, (size_t)n * h, st));
+    if (second) HIP_TRY(rows_to_host(second, second_pitch, ds, (size_t)w, (size_t)n * h, st));
+    if (margin) HIP_TRY(rows_to_host(margin, margin_pitch, dm, (size_t)4 * w, (size_t)n * h, st));
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, dh, (size_t)n * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_scores_confidence(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
+                                       uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
+                                       uint64_t* hist)
+{
+    const char* fn = "accel_scores_confidence";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const ConfStage cs(n, h, w, conf, margin, second, hist);
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    return confidence_to_host(fn, s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                              hist, ctx->stream);
+}
+
+extern "C" int accel_model_confidence(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch,
+                                      float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist, int dst_on_device)
+{
+    const char* fn = "accel_model_confidence";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)margin);
+        if (reinterpret_cast<uintptr_t>(hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)hist);
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                                  reinterpret_cast<unsigned long long*>(hist), st));
+        return 0;
+    }
+    const ConfStage cs(n, h, w, conf, margin, second, hist);
+    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
+    return confidence_to_host(fn, scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second,
+                              second_pitch, hist, st);
+}
+
+// ---- labels from interpolated scores (scores_labels.hip) ------------------------------------------------------------------------------------
+// What the four entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int scores_labels_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w)
+{
+    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the scores must have 2, 19 or 21 classes", fn, ncls);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    return 0;
+}
+
+extern "C" int accel_scores_labels(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                                   uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_scores_labels";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_scores_labels(s, n, ncls, H, W, out_h, out_w, h, w, d, (size_t)w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_model_scores_labels(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_scores_labels";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    if (dst_on_device) HIP_TRY(hipSetDevice(m->ctx->device));
+    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
+        return launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, d, pitch, st);
+    });
+}
+
+extern "C" int accel_model_scores_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                           int gt_on_device)
+{
+    const char* fn = "accel_model_scores_hist_add";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    const float* scores = nullptr;
+    int sncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &sncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, sncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    unsigned long long* hist = nullptr;
+    if (int rc = model_hist(fn, m, ncls, &hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+    unsigned char* lab = m->interp_labels.ptr;
+    const unsigned char* g = gt;
+    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
+    HIP_TRY(launch_scores_labels(scores, n, sncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
+    HIP_TRY(launch_labels_hist(lab, n, h, w, h, w, g, h, w, gt_pitch, ncls, hist, st));       // the scratch at the identity geometry
+    m->hist_ncls = ncls;
+    return 0;
+}
+
+extern "C" int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    const char* fn = "accel_model_scores_colour";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+    unsigned char* lab = m->interp_labels.ptr;
+    const unsigned char* f = frame_bgr;
+    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
+    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)3 * w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
+        const hipError_t e = launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st);
+        if (e != hipSuccess) return e;
+        return launch_labels_colour(lab, n, h, w, h, w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);   // the scratch at the identity geometry
+    });
+}
+
+extern "C" int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes)
+{
+    if (!m || !buf || !pinned_dst) return fail(ACCEL_ERR_ARG, "accel_model_read_async: NULL argument");
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "accel_model_read_async: unknown buffer '%s'", buf);
+    if (bytes > it->second.bytes) return fail(ACCEL_ERR_ARG, "accel_model_read_async: %zu bytes > buffer '%s' (%zu)", bytes, buf, it->second.bytes);
+    HIP_TRY(hipMemcpyAsync(pinned_dst, it->second.ptr, bytes, hipMemcpyDeviceToHost, m->ctx->stream));
+    return 0;
+}

@@ -166,7 +166,7 @@ hipError_t launch_ncls(const float* scores, int n, int H, int W, int out_h, int 
 
 }  // namespace
 
-// The callers (accel_hip.cpp confidence_args) have checked: n, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768, ncls in
+// The callers (accel_io.cpp confidence_args) have checked: n, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768, ncls in
 // {2, 19, 21}, pitches >= a row, margin_pitch % 4 == 0, at least one output.  Reads of `scores` stay inside out_h x out_w of each of the n * ncls
 // planes, writes inside w (4 * w) bytes of each of the n * h rows and the n * 256 words of hist, which are OVERWRITTEN (zeroed here first).
 hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob, unsigned char* conf,

@@ -196,7 +196,7 @@ const int32_t* nv12_coefficients(int colour)
     return colour >= 0 && colour < 4 ? NV12_COEF[colour] : nullptr;
 }
 
-// n NV12 frames in device memory -> n x 3 x H x W fp32 planar RGB.  The caller has checked the layout and the geometry (accel_hip.cpp
+// n NV12 frames in device memory -> n x 3 x H x W fp32 planar RGB.  The caller has checked the layout and the geometry (accel_io.cpp
 // frame_nv12_args): h, w even, pitch >= w, uv_offset >= h * pitch, frame_bytes >= uv_offset + (h / 2) * pitch, colour in 0 .. 3, out_h <= H,
 // out_w <= W, and step == 1 only with out_h == h, out_w == w.  Reads stay inside the two planes of every frame (the resampling coordinates
 // are clamped), writes inside H x W.  A width with w % 4 == 2 keeps the dword loads: only the patch the frame's edge cuts reads bytes.

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void frames_u8_resample_kernel(const unsigned 
 }  // namespace
 
 // n frames of h x w x 3 uint8 BGR, `pitch` bytes per row, h * pitch bytes per frame -> n x 3 x H x W fp32 planar RGB.  The caller has
-// checked the geometry (accel_hip.cpp frame_u8_args): out_h <= H, out_w <= W, pitch >= 3 * w, and step == 1 only with out_h == h,
+// checked the geometry (accel_io.cpp frame_u8_args): out_h <= H, out_w <= W, pitch >= 3 * w, and step == 1 only with out_h == h,
 // out_w == w.  Reads stay inside h x w (the resampling coordinates are clamped), writes inside H x W.
 hipError_t launch_frames_u8(const unsigned char* src, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
                             int H, int W, float* dst, hipStream_t st)

@@ -228,7 +228,7 @@ inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t
 
 }  // namespace
 
-// The callers (accel_hip.cpp results_args) have checked: n, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768, pitches >= a row.
+// The callers (accel_io.cpp results_args) have checked: n, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768, pitches >= a row.
 // Reads of `labels` stay inside out_h x out_w of each of the n maps (row and column indices are clamped), reads of gt / frame and writes of dst
 // inside w (3 * w) bytes of each of the n * h rows.
 hipError_t launch_labels_source(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,

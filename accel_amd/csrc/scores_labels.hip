@@ -118,7 +118,7 @@ hipError_t launch_ncls(const float* scores, int n, int H, int W, int out_h, int 
 
 }  // namespace
 
-// The callers (accel_hip.cpp scores_labels_args) have checked: 1 <= n <= 32768, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768,
+// The callers (accel_io.cpp scores_labels_args) have checked: 1 <= n <= 32768, h, w >= 1, 1 <= out_h <= H, 1 <= out_w <= W <= 32768, h, w <= 32768,
 // ncls in {2, 19, 21}, dst_pitch >= w.  Reads of `scores` stay inside out_h x out_w of each of the n * ncls planes (both taps of a row and of a
 // column are clamped into the region), writes inside the first w bytes of each of the n * h rows of dst.
 hipError_t launch_scores_labels(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,
