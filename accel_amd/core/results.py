@@ -2,7 +2,9 @@
 over as labels, as a colour image or as counts in a confusion matrix (csrc/results_u8.hip behind accel_model_labels_to_source /
 _labels_colour / _hist_add / _hist_read) -- and the logits themselves finished as a per-pixel confidence (csrc/confidence.hip behind
 accel_model_confidence), or as labels of their own: `interpolate=True` takes the LOGITS handle, interpolates the scores bilinearly to the
-source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour).
+source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour), and
+`confidence(..., interpolate=True)` takes the confidence from those interpolated scores too, with the labels if asked, in one pass
+(csrc/scores_confidence.hip behind accel_model_confidence_interp).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -85,17 +87,28 @@ def colour(handle, like, palette, frames=None, alpha=256, rgb=True, interpolate=
     return m.labels_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
 
 
-def confidence(handle, like, margin=False, second=False, hist=False, probabilities=None):
+def confidence(handle, like, margin=False, second=False, hist=False, probabilities=None, interpolate=False, labels=False):
     """How sure the network was, per source pixel, from the LOGITS handle a Predictor returned (not the label handle): conf, numpy
     n x h x w uint8 = min(255, floor(256 * largest softmax probability)) -- or the tuple (conf[, margin][, second][, hist]) with what
     was asked for: margin n x h x w float32 = top score - runner-up score, second n x h x w uint8 = the runner-up class, hist
-    n x 256 uint64 = pixels per conf level of each frame (utils.image.confidence_host, on the GPU).  probabilities: the stored scores
-    are probabilities already (a tail lowered with softmax=1); None takes the answer from the handle."""
+    n x 256 uint64 = pixels per conf level of each frame (utils.image.confidence_host, on the GPU: the scores of the nearest map pixel,
+    pixel for pixel with labels_at_source under the nearest rule).  probabilities: the stored scores are probabilities already (a tail
+    lowered with softmax=1); None takes the answer from the handle.
+    interpolate=True: everything is taken from the scores interpolated bilinearly to the source pixel, pixel for pixel with
+    labels_at_source(handle, like, interpolate=True) (utils.image.confidence_interpolated_host, on the GPU, one pass over the logits).
+    labels=True (needs interpolate=True; under the nearest rule the label handle already exists) prepends that label map, n x h x w uint8:
+    (labels, conf[, margin][, second][, hist])."""
+    if labels and not interpolate:
+        raise ValueError("labels=True needs interpolate=True: under the nearest rule the labels are those of the label handle (labels_at_source)")
     m = _model(handle, "logits")
     n, out_h, out_w, h, w = _geometry(handle, like, scores=True)
     if probabilities is None:
         probabilities = bool(getattr(handle, "probabilities", False))
-    out = m.confidence(n, out_h, out_w, h, w, is_prob=probabilities, conf=True, margin=bool(margin), second=bool(second), hist=bool(hist))
+    want = dict(is_prob=probabilities, conf=True, margin=bool(margin), second=bool(second), hist=bool(hist))
+    if interpolate:
+        out = m.confidence_interp(n, out_h, out_w, h, w, labels=bool(labels), **want)
+    else:
+        out = m.confidence(n, out_h, out_w, h, w, **want)
     out = tuple(a for a in out if a is not None)
     return out[0] if len(out) == 1 else out
 

@@ -1,6 +1,6 @@
 // libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
-// points behind them -- uint8 and NV12 frames in, finished frames, confidence and interpolated labels out (see include/accel_hip.h).  Nothing
-// here knows about plans.
+// points behind them -- uint8 and NV12 frames in, finished frames, confidence (of stored and of interpolated scores) and interpolated labels out
+// (see include/accel_hip.h).  Nothing here knows about plans.
 #include <cstring>
 
 #include "accel_objects.h"
@@ -648,13 +648,17 @@ extern "C" int accel_model_labels_colour(accel_model* m, int n, int out_h, int o
 
 // ---- confidence of finished frames (confidence.hip) ----------------------------------------------------------------------------------------
 // What the two entry points share, checked before anything is enqueued: every message names the argument at fault.
+// (`with_labels`: the entry point has a labels output at all -- the interpolated forms; the others pass false, NULL, 0)
 static int confidence_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, const void* conf, size_t conf_pitch,
-                           const void* margin, size_t margin_pitch, const void* second, size_t second_pitch, const void* hist)
+                           const void* margin, size_t margin_pitch, const void* second, size_t second_pitch, const void* hist,
+                           bool with_labels = false, const void* labels = nullptr, size_t labels_pitch = 0)
 {
-    if (!conf && !margin && !second && !hist) return fail(ACCEL_ERR_ARG, "%s: conf, margin, second and hist are all NULL: nothing to compute", fn);
+    if (!labels && !conf && !margin && !second && !hist)
+        return fail(ACCEL_ERR_ARG, "%s: %sconf, margin, second and hist are all NULL: nothing to compute", fn, with_labels ? "labels, " : "");
     if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be 2, 19 or 21", fn, ncls);
     if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
     if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    if (labels) if (int rc = pitch_arg(fn, "labels_pitch", labels_pitch, w, 1)) return rc;
     if (conf) if (int rc = pitch_arg(fn, "conf_pitch", conf_pitch, w, 1)) return rc;
     if (margin) {
         if (int rc = pitch_arg(fn, "margin_pitch", margin_pitch, w, 4)) return rc;
@@ -664,14 +668,15 @@ static int confidence_args(const char* fn, int n, int ncls, int H, int W, int ou
     return 0;
 }
 
-// the device side of a call whose results go to the host: tight rows in `base` (conf, second: n * h * w bytes; margin: 4 times that; hist: n * 256
-// words), each part 256-byte aligned
+// the device side of a call whose results go to the host: tight rows in `base` (labels, conf, second: n * h * w bytes; margin: 4 times that; hist:
+// n * 256 words), each part 256-byte aligned
 struct ConfStage {
-    size_t conf = 0, second = 0, margin = 0, hist = 0, bytes = 0;
-    ConfStage(int n, int h, int w, bool c, bool mg, bool s, bool hi)
+    size_t labels = 0, conf = 0, second = 0, margin = 0, hist = 0, bytes = 0;
+    ConfStage(int n, int h, int w, bool c, bool mg, bool s, bool hi, bool lab = false)
     {
         const size_t px = (size_t)n * h * w;
         auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
+        if (lab) labels = take(px);
         if (c) conf = take(px);
         if (s) second = take(px);
         if (mg) margin = take(px * 4);
@@ -679,15 +684,21 @@ struct ConfStage {
     }
 };
 
+// `interp`: the interpolated form (launch_scores_confidence, which can also hand out `labels`) instead of the nearest one (launch_confidence)
 static int confidence_to_host(const char* fn, const float* scores, unsigned char* base, const ConfStage& cs, int n, int ncls, int H, int W, int out_h, int out_w,
                               int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second,
-                              size_t second_pitch, uint64_t* hist, hipStream_t st)
+                              size_t second_pitch, uint64_t* hist, hipStream_t st, bool interp = false, uint8_t* labels = nullptr, size_t labels_pitch = 0)
 {
+    unsigned char* dl = labels ? base + cs.labels : nullptr;
     unsigned char* dc = conf ? base + cs.conf : nullptr;
     unsigned char* ds = second ? base + cs.second : nullptr;
     float* dm = margin ? reinterpret_cast<float*>(base + cs.margin) : nullptr;
     unsigned long long* dh = hist ? reinterpret_cast<unsigned long long*>(base + cs.hist) : nullptr;
-    HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
+    if (interp)
+        HIP_TRY(launch_scores_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dl, (size_t)w, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
+    else
+        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
+    if (labels) HIP_TRY(rows_to_host(labels, labels_pitch, dl, (size_t)w, (size_t)n * h, st));
     if (conf) HIP_TRY(rows_to_host(conf, conf_pitch, dc, (size_t)w, (size_t)n * h, st));
     if (second) HIP_TRY(rows_to_host(second, second_pitch, ds, (size_t)w, (size_t)n * h, st));
     if (margin) HIP_TRY(rows_to_host(margin, margin_pitch, dm, (size_t)4 * w, (size_t)n * h, st));
@@ -736,6 +747,54 @@ extern "C" int accel_model_confidence(accel_model* m, int n, int out_h, int out_
     if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
     return confidence_to_host(fn, scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second,
                               second_pitch, hist, st);
+}
+
+// ---- confidence of interpolated scores, with their labels (scores_confidence.hip) ------------------------------------------------------------------
+extern "C" int accel_scores_confidence_interp(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                                              int is_prob, uint8_t* labels, size_t labels_pitch, uint8_t* conf, size_t conf_pitch, float* margin,
+                                              size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist)
+{
+    const char* fn = "accel_scores_confidence_interp";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist, true, labels,
+                                 labels_pitch))
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const ConfStage cs(n, h, w, conf, margin, second, hist, labels);
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    return confidence_to_host(fn, s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
+                              hist, ctx->stream, true, labels, labels_pitch);
+}
+
+extern "C" int accel_model_confidence_interp(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* labels, size_t labels_pitch,
+                                             uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
+                                             uint64_t* hist, int dst_on_device)
+{
+    const char* fn = "accel_model_confidence_interp";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist, true, labels,
+                                 labels_pitch))
+        return rc;
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)margin);
+        if (reinterpret_cast<uintptr_t>(hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)hist);
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        HIP_TRY(launch_scores_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, labels, labels_pitch, conf, conf_pitch, margin, margin_pitch,
+                                         second, second_pitch, reinterpret_cast<unsigned long long*>(hist), st));
+        return 0;
+    }
+    const ConfStage cs(n, h, w, conf, margin, second, hist, labels);
+    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
+    return confidence_to_host(fn, scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second,
+                              second_pitch, hist, st, true, labels, labels_pitch);
 }
 
 // ---- labels from interpolated scores (scores_labels.hip) ------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 // non-zero bin per block into the frame's 256 words (as labels_hist_kernel does).  blockIdx.z is the frame: a block never spans two.
 // Integer sums: exact, independent of the order of arrival.  The kernel only READS the scores.
 #include "kernels.h"
+#include "levels_hist.h"
 #include <stdint.h>
 
 namespace {
@@ -113,33 +114,11 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
         }
         if (want_hist) {
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                if (c[j] == key) {
-                    ++cnt;
-                } else {
-                    if (cnt) atomicAdd(&bins[key], cnt);
-                    key = c[j]; cnt = 1;
-                }
-            }
+            for (int j = 0; j < V; ++j) levels::count(bins, key, cnt, c[j]);
         }
     }
 
-    if (want_hist) {
-        // the run every lane still holds: one add for the wavefront when it is the same level in all of them (a saturated region)
-        const unsigned lk = __builtin_amdgcn_readfirstlane(key);
-        if (!cnt) key = lk;       // a lane that counted nothing agrees with anyone
-        if (__all(key == lk)) {
-            unsigned sum = cnt;
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
-            if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&bins[lk], sum);
-        } else if (cnt) {
-            atomicAdd(&bins[key], cnt);
-        }
-        __syncthreads();
-        const unsigned v = bins[threadIdx.x];
-        if (v) atomicAdd(&o.hist[(size_t)z * 256 + threadIdx.x], (unsigned long long)v);
-    }
+    if (want_hist) levels::flush(bins, key, cnt, o.hist + (size_t)z * 256);
 }
 
 inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }

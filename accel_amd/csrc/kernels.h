@@ -184,6 +184,13 @@ hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W,
 // labels_interpolated_host), n x h x w uint8 with rows dst_pitch bytes apart.  Device pointers; the kernel only reads `scores`
 hipError_t launch_scores_labels(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,
                                 hipStream_t st);
+// confidence of interpolated scores, with their labels (scores_confidence.hip): the same scores and geometry -> per source pixel, from the ncls values
+// v_k interpolated as launch_scores_labels interpolates them, labels = its argmax, conf / margin / second / hist as launch_confidence but of the v_k
+// (float64 throughout; margin = float(v_top1 - v_top2); utils/image.py confidence_interpolated_host).  A null output is left out, at least one is
+// given; pitches in bytes (margin_pitch a multiple of 4); hist is overwritten.  Device pointers; the kernel only reads `scores`
+hipError_t launch_scores_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
+                                    unsigned char* labels, size_t labels_pitch, unsigned char* conf, size_t conf_pitch, float* margin, size_t margin_pitch,
+                                    unsigned char* second, size_t second_pitch, unsigned long long* hist, hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

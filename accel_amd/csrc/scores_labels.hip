@@ -5,11 +5,7 @@
 // The geometry vocabulary is that of results_u8.hip and confidence.hip: one valid region out_h x out_w in the top-left corner of the H x W
 // map, one source size h x w.  The arithmetic restates accel_amd/utils/image.py labels_interpolated_host bit for bit.
 //
-// Taps, in integer arithmetic (source row y of h rows over a region of out_h rows; columns alike with w, out_w):
-//     num = clamp((2 * y + 1) * out_h - h, 0, 2 * h * (out_h - 1))           (< 2^31: sizes are at most 32768)
-//     y0  = num / (2 * h);   y1 = min(y0 + 1, out_h - 1);   fy = double(num - 2 * h * y0) / double(2 * h)        ONE IEEE division
-// which is the half-pixel-centre coordinate (y + 0.5) * out_h / h - 0.5 clamped to the region: the inverse of the resize the frame went
-// through on the way in (frames_resample.h).  Taps never leave the valid region: the padding is never read.
+// Taps: scores_interp.h (integer arithmetic, clamped to the valid region -- the padding is never read -- one IEEE division per weight).
 // Blend, in float64, each operation rounded on its own (no fma), in the order of frames::blend; a<row><col> the fp32 taps as doubles:
 //     gx = 1 - fx;  gy = 1 - fy;  top = a00 * gx + a01 * fx;  bot = a10 * gx + a11 * fx;  v_k = top * gy + bot * fy
 // Label: the first k with the largest v_k (ascending scan, strict >): the tie rule of `labels`.
@@ -22,23 +18,13 @@
 // an fp32 compare chain (the blend is the identity there) and one dword store of four labels.
 // Grid-stride loop, no LDS, no atomics.  blockIdx.z is the frame.  The kernel only READS the scores.
 #include "kernels.h"
+#include "scores_interp.h"
 #include <stdint.h>
 
 namespace {
 
-struct Tap { int i0, i1; double f; };
-
-// the two taps and the weight of the second for output index i of `dst` over a region of `src`
-__device__ __forceinline__ Tap tap(int i, int dst, int src)
-{
-    const int two = 2 * dst;
-    const int num = min(max((2 * i + 1) * src - dst, 0), two * (src - 1));
-    Tap t;
-    t.i0 = num / two;
-    t.i1 = min(t.i0 + 1, src - 1);
-    t.f = (double)(num - two * t.i0) / (double)two;
-    return t;
-}
+using interp::Tap;
+using interp::tap;
 
 template <int NCLS, int V>
 __global__ __launch_bounds__(256) void scores_labels_kernel(const float* __restrict__ scores, int H, int W, int out_h, int out_w, int h, int w,

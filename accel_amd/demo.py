@@ -196,7 +196,8 @@ def main(argv=None):
     ap.add_argument('--confidence', action='store_true',
                     help='with --finish-on-gpu: per frame, the mean confidence (largest softmax probability) and the share of pixels '
                          'below level 128 of 256, from a histogram made on the GPU where the logits are; --out also writes '
-                         'conf_<frame>.png in greyscale')
+                         'conf_<frame>.png in greyscale.  With --interpolate the confidence is that of the interpolated scores, the '
+                         'ones the labels are the argmax of, and both come from one pass over the logits inside the timed loop')
     ap.add_argument('--interpolate', action='store_true',
                     help='with --finish-on-gpu: the labels at the source size are the argmax of the bilinearly INTERPOLATED scores '
                          '(made on the GPU where the logits are) instead of the nearest label of the finished map; the mIoU counts them')
@@ -278,7 +279,11 @@ def main(argv=None):
         lg, lab = runner.step(idx, arrays, interv)
         if idx + 1 < len(data) and not args.pageable:
             runner.prefetch(data[idx + 1])        # next frame starts crossing PCIe while this one computes
-        if args.finish_on_gpu:
+        fused = args.finish_on_gpu and args.interpolate and args.confidence       # labels, conf and hist from ONE pass over the logits
+        if fused:
+            pred, conf, conf_hist = results.confidence(lg, source, interpolate=True, labels=True, hist=True)
+            pred = pred[0]
+        elif args.finish_on_gpu:
             pred = (results.labels_at_source(lg, source, interpolate=True) if args.interpolate else results.labels_at_source(lab, source))[0]
         else:
             pred = np.uint8(np.squeeze(lab.asnumpy()))
@@ -287,7 +292,8 @@ def main(argv=None):
         count += 1
         print('testing {} {:.4f}s [{:.4f}s]'.format(names[idx], elapsed, time_sum / count))
         if args.confidence:       # after the clock: the histogram is 2 KB, the map a byte per source pixel
-            conf, conf_hist = results.confidence(lg, source, hist=True)
+            if not fused:
+                conf, conf_hist = results.confidence(lg, source, hist=True)
             mean, low = results.confidence_summary(conf_hist[0])
             print('confidence mean {:.4f} below-128 {:.4f}'.format(mean, low))
             if args.out:

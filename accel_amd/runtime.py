@@ -91,6 +91,8 @@ def _declare(lib):
         "accel_model_labels_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
         "accel_scores_confidence": [vp, vp, i, i, i, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp],
         "accel_model_confidence": [vp, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp, i],
+        "accel_scores_confidence_interp": [vp, vp, i, i, i, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp, sz, vp],
+        "accel_model_confidence_interp": [vp, i, i, i, i, i, i, vp, sz, vp, sz, vp, sz, vp, sz, vp, i],
         "accel_scores_labels": [vp, vp, i, i, i, i, i, i, i, i, vp, sz],
         "accel_model_scores_labels": [vp, i, i, i, i, i, vp, sz, i],
         "accel_model_scores_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
@@ -247,13 +249,15 @@ def _result_rows(out, n, h, w, channels):
     return out, out.shape[2]
 
 
-def _confidence_outputs(n, h, w, conf, margin, second, hist):
+def _confidence_outputs(n, h, w, conf, margin, second, hist, labels=None):
     """the destinations of a confidence call: for conf, margin and second True (a fresh tight array), False / None (left out) or the
     caller's array of n x h x pitch elements (uint8, for margin float32: pitch * 4 bytes per row), of which only the first w of every
     row are written; `hist` True or False.  Returns ([conf, margin, second, hist], [(pointer, pitch in bytes)] of the first three,
-    hist pointer), with None / (None, 0) for what is left out."""
+    hist pointer), with None / (None, 0) for what is left out.  labels (the interpolated forms; not None): the same rule as conf, and
+    it comes first in both lists."""
     outs, ptrs = [], []
-    for want, dtype, what in ((conf, np.uint8, "conf"), (margin, np.float32, "margin"), (second, np.uint8, "second")):
+    first = () if labels is None else ((labels, np.uint8, "labels"),)
+    for want, dtype, what in first + ((conf, np.uint8, "conf"), (margin, np.float32, "margin"), (second, np.uint8, "second")):
         if want is None or want is False:
             outs.append(None)
             ptrs.append((None, 0))
@@ -441,6 +445,19 @@ class Context(object):
         outs, p, hp = _confidence_outputs(n, int(h), int(w), conf, margin, second, hist)
         check(lib().accel_scores_confidence(self.handle, _fp(a), n, ncls, H, W, int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
                                             p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], hp))
+        return tuple(outs)
+
+    def scores_confidence_interp(self, scores, out_h, out_w, h, w, is_prob=False, labels=True, conf=True, margin=True, second=True, hist=True):
+        """accel_scores_confidence_interp: n x ncls x H x W scores whose valid region is out_h x out_w -> (labels, conf, margin, second, hist)
+        at the source size h x w, all five from the bilinearly interpolated scores (utils.image.confidence_interpolated_host); the
+        arguments are those of scores_confidence, labels like conf"""
+        a = _f32(scores)
+        if a.ndim != 4:
+            raise ValueError("scores must be n x ncls x H x W fp32, got shape %s" % (a.shape,))
+        n, ncls, H, W = a.shape
+        outs, p, hp = _confidence_outputs(n, int(h), int(w), conf, margin, second, hist, labels=False if labels is None else labels)
+        check(lib().accel_scores_confidence_interp(self.handle, _fp(a), n, ncls, H, W, int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                                   p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], p[3][0], p[3][1], hp))
         return tuple(outs)
 
     def scores_labels(self, scores, out_h, out_w, h, w, out=None):
@@ -786,6 +803,22 @@ class Model(object):
         check(lib().accel_model_confidence(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
                                            vp(conf_ptr), int(conf_pitch), vp(margin_ptr), int(margin_pitch), vp(second_ptr), int(second_pitch),
                                            vp(hist_ptr), 1))
+
+    def confidence_interp(self, n, out_h, out_w, h, w, is_prob=False, labels=True, conf=True, margin=True, second=True, hist=True):
+        """accel_model_confidence_interp: (labels, conf, margin, second, hist) of the first n frames of `logits` interpolated to the source
+        size h x w, as numpy arrays (see Context.scores_confidence_interp for the arguments); it only READS `logits`"""
+        outs, p, hp = _confidence_outputs(int(n), int(h), int(w), conf, margin, second, hist, labels=False if labels is None else labels)
+        check(lib().accel_model_confidence_interp(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                                  p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], p[3][0], p[3][1], hp, 0))
+        return tuple(outs)
+
+    def confidence_interp_device(self, n, out_h, out_w, h, w, is_prob=False, labels_ptr=None, labels_pitch=0, conf_ptr=None, conf_pitch=0,
+                                 margin_ptr=None, margin_pitch=0, second_ptr=None, second_pitch=0, hist_ptr=None):
+        """the same into caller-owned HBM (enqueued, no host wait): device pointers, pitches in bytes; hist_ptr names n x 256 uint64"""
+        vp = lambda v: ctypes.c_void_p(v) if v else None
+        check(lib().accel_model_confidence_interp(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
+                                                  vp(labels_ptr), int(labels_pitch), vp(conf_ptr), int(conf_pitch), vp(margin_ptr), int(margin_pitch),
+                                                  vp(second_ptr), int(second_pitch), vp(hist_ptr), 1))
 
     # ---- labels from interpolated scores: they only READ `logits` ------------------------------------------------------------
     def scores_labels(self, n, out_h, out_w, h, w, out=None):

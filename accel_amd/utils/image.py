@@ -188,6 +188,55 @@ def labels_interpolated_host(scores, out_h, out_w, h, w):
     return label
 
 
+def confidence_interpolated_host(scores, out_h, out_w, h, w, is_prob=False):
+    """The specification of accel_scores_confidence_interp, in float64: scores n x ncls x H x W fp32 (valid region out_h x out_w in the
+    top-left corner) -> (labels, conf, margin, second, hist) at the source size h x w, from the values v_k every class plane takes when it is
+    interpolated to the source pixel exactly as labels_interpolated_host does it (interpolation_taps clamped to the region -- the padding is
+    never read; the float64 blend with every operation rounded on its own, in that function's order).  Scores are assumed finite.
+      labels  uint8    the first k with the largest v_k: labels_interpolated_host
+      conf    uint8    min(255, floor(256 * p)), p = 1 / sum_k exp(v_k - v_best), classes summed in ascending order: the softmax of the
+                       interpolated logits, whose argmax is the label; is_prob: the stored values are probabilities, blended the same way,
+                       min(255, floor(256 * v_best)) -- no exponential, exact everywhere
+      margin  float32  float32(v_best - v_second): one float64 subtraction, rounded once to fp32; 0 on a tie at the top
+      second  uint8    the first maximal index among the classes other than the label, compared on the float64 v_k
+      hist    uint64   n x 256: the number of source pixels of each frame at each conf level
+    At h x w == out_h x out_w every weight is 0 and v_k is the stored score: confidence_host plus the crop of the argmax."""
+    s = np.asarray(scores, np.float32)
+    if s.ndim != 4 or s.shape[1] < 2:
+        raise ValueError("scores must be n x ncls x H x W with ncls >= 2, got shape %s" % (s.shape,))
+    n, ncls = s.shape[:2]
+    if not (1 <= int(out_h) <= s.shape[2] and 1 <= int(out_w) <= s.shape[3]):
+        raise ValueError("the valid region %d x %d does not lie in the %d x %d map" % (out_h, out_w, s.shape[2], s.shape[3]))
+    y0, y1, fy = interpolation_taps(h, out_h)
+    x0, x1, fx = interpolation_taps(w, out_w)
+    fy, fx = fy[None, :, None], fx[None, None, :]
+    gy, gx = 1 - fy, 1 - fx
+    v = np.empty((n, ncls, int(h), int(w)), np.float64)
+    for k in range(ncls):
+        a = s[:, k, :int(out_h), :int(out_w)].astype(np.float64)
+        r0, r1 = a[:, y0], a[:, y1]
+        top = r0[:, :, x0] * gx + r0[:, :, x1] * fx
+        bot = r1[:, :, x0] * gx + r1[:, :, x1] * fx
+        v[:, k] = top * gy + bot * fy
+    best = np.argmax(v, axis=1)                                   # the first maximal index
+    top1 = np.take_along_axis(v, best[:, None], axis=1)[:, 0]
+    is_best = np.arange(ncls).reshape(1, ncls, 1, 1) == best[:, None]
+    others = np.where(is_best, -np.inf, v)
+    second = np.argmax((others == others.max(axis=1, keepdims=True)) & ~is_best, axis=1)
+    top2 = np.take_along_axis(v, second[:, None], axis=1)[:, 0]
+    margin = (top1 - top2).astype(np.float32)
+    if is_prob:
+        scaled = 256.0 * top1
+    else:
+        total = np.zeros(top1.shape, np.float64)
+        for k in range(ncls):
+            total += np.exp(v[:, k] - top1)
+        scaled = 256.0 * (1.0 / total)
+    conf = np.minimum(255.0, np.floor(scaled)).astype(np.uint8)
+    hist = np.stack([np.bincount(c.reshape(-1), minlength=256) for c in conf]).astype(np.uint64)
+    return best.astype(np.uint8), conf, margin, second.astype(np.uint8), hist
+
+
 def transform(im, pixel_means):
     """Contract of lib/utils/image.py:224-235: a BGR H x W x 3 frame becomes the 1 x 3 x H x W RGB tensor with the per-channel
     mean removed (`pixel_means` is given in B, G, R order like the frame).  float64 like the reference; arrays become fp32

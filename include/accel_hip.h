@@ -360,6 +360,32 @@ int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h
                               const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
                               uint8_t* dst, size_t dst_pitch, int dst_on_device);
 
+/* ---- finished frames: confidence of interpolated scores, with their labels ---------------------------------------------
+ * The confidence block above describes the NEAREST map pixel; the labels of the block above are the argmax of INTERPOLATED
+ * scores.  For a frame that was resampled on the way in the two do not speak of the same winner.  These two calls finish a
+ * source pixel from the interpolated values themselves, in ONE pass over the scores (csrc/scores_confidence.hip), and can
+ * hand out the label found on the way.  `scores`, ncls and the geometry as above; v_k are the ncls values of the pixel,
+ * taps and blend exactly as in the block above (float64).  Any subset of (a NULL pointer leaves one out, at least one):
+ *   labels   n x h x w uint8    the first k with the largest v_k: what accel_scores_labels writes
+ *   conf     n x h x w uint8    min(255, floor(256 * p)), p = 1 / sum_k exp(v_k - v_best), classes in ascending order, all
+ *                               in float64: the softmax of the interpolated logits, whose argmax is `labels`
+ *   margin   n x h x w fp32     float(v_best - v_second): one float64 subtraction, rounded once to fp32; 0 on a tie at the top
+ *   second   n x h x w uint8    the first maximal index among the classes other than `labels`, compared on the float64 v_k
+ *   hist     n x 256 uint64     per frame, the number of source pixels at each conf level: OVERWRITTEN
+ * is_prob = 1: the stored values are probabilities and are blended the same way; conf = min(255, floor(256 * v_best)), no
+ * exponential.  The specification is accel_amd/utils/image.py confidence_interpolated_host; the kernel restates it bit for
+ * bit up to the exp.  At h x w == out_h x out_w every weight is 0: the outputs are those of accel_scores_confidence and the
+ * crop of `labels`.  Scores are assumed FINITE.  Pitches, argument errors and dst_on_device as for accel_model_confidence,
+ * with labels / labels_pitch checked like conf / conf_pitch.
+ *   accel_scores_confidence_interp   operator level: host scores in, host results out (the parity tests)
+ *   accel_model_confidence_interp    on the model's `logits` buffer; it only reads `logits` */
+int accel_scores_confidence_interp(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
+                                   uint8_t* labels, size_t labels_pitch, uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch,
+                                   uint8_t* second, size_t second_pitch, uint64_t* hist);
+int accel_model_confidence_interp(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* labels, size_t labels_pitch,
+                                  uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
+                                  uint64_t* hist, int dst_on_device);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
