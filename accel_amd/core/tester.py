@@ -26,7 +26,7 @@ import numpy as np
 
 from .. import lower as _lower
 from .. import runtime
-from ..mx.ndarray import DeviceArray, NV12Frames, RawFrames
+from ..mx.ndarray import DeviceArray, NV12Frames, RawFrames, YUVFrames
 
 _MODELS = {}   # (device id, N, H, W, parameter token, owner) -> runtime.Model: the key and cur plans of one demo share buffers
 
@@ -212,6 +212,8 @@ class Predictor(object):
             if tag is not None and pre.get("data") == tag:
                 if isinstance(data, NV12Frames):     # its BYTES were prefetched (the same uint8 shadow): colour conversion included
                     m.commit_nv12("data", *_nv12_layout(data), **data.geometry)
+                elif isinstance(data, YUVFrames):    # I420 / P010 / YUY2 bytes, through the same uint8 shadow
+                    m.commit_yuv("data", data.layout["n"], data.layout, data.means, **data.geometry)
                 elif isinstance(data, RawFrames):    # its BYTES were prefetched (uint8 shadow): converted on the way into `data`
                     m.commit_u8("data", *_u8_layout(data), **data.geometry)
                 else:
@@ -300,7 +302,7 @@ class Predictor(object):
         pb = getattr(data_array, "pinned", None)
         if pb is None or self._model is None:
             return False
-        if isinstance(data_array, RawFrames):       # uint8 bytes, BGR or NV12: a quarter or an eighth of the fp32 tensor crosses PCIe, into a shadow of their own
+        if isinstance(data_array, RawFrames):       # uint8 bytes -- BGR, NV12, I420, P010 or YUY2: a quarter of the fp32 tensor or less crosses PCIe, into a shadow of their own
             self._model.prefetch_u8("data", pb)
         else:
             self._model.prefetch("data", pb)
@@ -335,11 +337,16 @@ def _nv12_layout(raw):
 
 def _write_image(m, buf, arr):
     """an image input that is not in HBM yet: raw uint8 frames are uploaded as bytes and resized / centred / padded by the GPU
-    (accel_model_write_u8; NV12 bytes: accel_model_write_nv12, which converts the colour too), anything else is the fp32 tensor itself"""
+    (accel_model_write_u8; NV12 bytes: accel_model_write_nv12, I420 / P010 / YUY2 bytes: accel_model_write_yuv, which convert the colour
+    too), anything else is the fp32 tensor itself"""
     if isinstance(arr, NV12Frames):
         lay = arr.layout
         m.write_nv12(buf, arr.nv12, lay["h"], lay["w"], arr.means, pitch=lay["pitch"], uv_offset=lay["uv_offset"], frame_bytes=lay["frame_bytes"],
                      colour=lay["colour"], **arr.geometry)
+    elif isinstance(arr, YUVFrames):       # (NV12Frames and YUVFrames are siblings under RawFrames: both are asked before it)
+        lay = arr.layout
+        m.write_yuv(buf, arr.yuv, lay["format"], lay["h"], lay["w"], arr.means, colour=lay["colour"],
+                    **{k: lay[k] for k in ("pitch", "pitch_c", "u_offset", "v_offset", "frame_bytes")}, **arr.geometry)
     elif isinstance(arr, RawFrames):
         m.write_u8(buf, arr.frames, arr.means, **arr.geometry)
     else:

@@ -1,5 +1,5 @@
 // libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
-// points behind them -- uint8 and NV12 frames in, finished frames, confidence (of stored and of interpolated scores) and interpolated labels out
+// points behind them -- uint8, NV12, I420, P010 and YUY2 frames in, finished frames, confidence (of stored and of interpolated scores) and interpolated labels out
 // (see include/accel_hip.h).  Nothing here knows about plans.
 #include <cstring>
 
@@ -399,6 +399,168 @@ extern "C" int accel_model_commit_nv12(accel_model* m, const char* buf, int n, i
                     need, sh->filled, buf);
     return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
         return launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
+    });
+}
+
+// ---- I420, P010 and YUY2 frames (frames_yuv.hip) ----------------------------------------------------------------------------------
+extern "C" int accel_yuv10_coefficients(int colour, int32_t out[6])
+{
+    if (!out) return fail(ACCEL_ERR_ARG, "accel_yuv10_coefficients: out is NULL");
+    const int32_t* c = yuv10_coefficients(colour);
+    if (!c) return fail(ACCEL_ERR_ARG, "accel_yuv10_coefficients: colour = %d, must be in 0 .. 3", colour);
+    for (int i = 0; i < 6; ++i) out[i] = c[i];
+    return 0;
+}
+
+enum { YUV_I420 = 0, YUV_P010 = 1, YUV_YUY2 = 2 };
+
+// the bytes one frame occupies: one past the last byte of the last row of its last plane (planes of I420 may interleave, so no whole pitch is
+// counted for the last row)
+static size_t yuv_extent(const accel_yuv_layout& y)
+{
+    const size_t h = (size_t)y.h, w = (size_t)y.w;
+    if (y.format == YUV_I420) return (y.u_offset > y.v_offset ? y.u_offset : y.v_offset) + (h / 2 - 1) * y.pitch_c + w / 2;
+    if (y.format == YUV_P010) return y.u_offset + (h / 2 - 1) * y.pitch + 2 * w;
+    return (h - 1) * y.pitch + 2 * w;
+}
+
+// the bytes n frames occupy: the last one ends with its extent
+static size_t yuv_bytes(int n, const accel_yuv_layout& y)
+{
+    return (size_t)(n - 1) * y.frame_bytes + yuv_extent(y);
+}
+
+// Layout of I420 / P010 / YUY2 frames, checked before anything is enqueued: every message names the argument at fault.  `dev`: the address the
+// kernel will read if the caller's pointer is device memory, else NULL (host bytes are uploaded into an aligned buffer).
+static int yuv_layout_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, const void* dev)
+{
+    const int lim = 32768;
+    static const char* const names[3] = {"I420", "P010", "YUY2"};
+    if (!yuv) return fail(ACCEL_ERR_ARG, "%s: yuv is NULL", fn);
+    if (!lay) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
+    const accel_yuv_layout& y = *lay;
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (y.format < 0 || y.format > 2) return fail(ACCEL_ERR_ARG, "%s: format = %d, must be 0 (I420), 1 (P010) or 2 (YUY2)", fn, y.format);
+    const char* name = names[y.format];
+    if (y.colour < 0 || y.colour > 3)
+        return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, y.colour);
+    const bool even_h = y.format != YUV_YUY2;
+    if (y.h < 1 || y.h > lim || (even_h && y.h % 2)) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be %sin 1 .. %d for %s", fn, y.h, even_h ? "even and " : "", lim, name);
+    if (y.w < 1 || y.w > lim || y.w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 1 .. %d for %s", fn, y.w, lim, name);
+    const size_t row = y.format == YUV_I420 ? (size_t)y.w : (size_t)2 * y.w;
+    if (y.pitch < row) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d %s pixels has %zu", fn, y.pitch, y.w, name, row);
+    if (y.pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, y.pitch);
+    const size_t luma_end = (size_t)y.h * y.pitch;
+    if (y.format == YUV_I420) {
+        if (y.pitch_c < (size_t)y.w / 2) return fail(ACCEL_ERR_ARG, "%s: pitch_c = %zu bytes, a chroma row of w = %d I420 pixels has %d", fn, y.pitch_c, y.w, y.w / 2);
+        if (y.pitch_c > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch_c = %zu bytes is not a row pitch", fn, y.pitch_c);
+    } else {
+        if (y.pitch_c) return fail(ACCEL_ERR_ARG, "%s: pitch_c = %zu, but %s has no such field: it must be 0", fn, y.pitch_c, name);
+        if (y.v_offset) return fail(ACCEL_ERR_ARG, "%s: v_offset = %zu, but %s has no such field: it must be 0", fn, y.v_offset, name);
+        if (y.format == YUV_YUY2 && y.u_offset) return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu, but YUY2 has no such field: it must be 0", fn, y.u_offset);
+    }
+    if (y.format != YUV_YUY2 && (y.u_offset < luma_end || y.u_offset > ((size_t)1 << 60)))
+        return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.u_offset, y.h, y.pitch, luma_end);
+    if (y.format == YUV_I420 && (y.v_offset < luma_end || y.v_offset > ((size_t)1 << 60)))
+        return fail(ACCEL_ERR_ARG, "%s: v_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.v_offset, y.h, y.pitch, luma_end);
+    if (y.frame_bytes < yuv_extent(y))
+        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the last plane of a frame ends at %zu", fn, y.frame_bytes, yuv_extent(y));
+    if (y.frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, y.frame_bytes);
+    if (y.format == YUV_P010) {       // every 16-bit word is read as one
+        if (y.pitch % 2) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu, P010 words are 2-byte aligned: it must be even", fn, y.pitch);
+        if (y.u_offset % 2) return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu, P010 words are 2-byte aligned: it must be even", fn, y.u_offset);
+        if (y.frame_bytes % 2) return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, P010 words are 2-byte aligned: it must be even", fn, y.frame_bytes);
+        if (reinterpret_cast<uintptr_t>(dev) % 2) return fail(ACCEL_ERR_ARG, "%s: yuv = %p, P010 words are 2-byte aligned: a device address must be even", fn, dev);
+    }
+    return 0;
+}
+
+static int frame_yuv_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, const void* dev, const double* means_bgr, int out_h,
+                          int out_w, double step, int H, int W)
+{
+    if (int rc = yuv_layout_args(fn, yuv, n, lay, dev)) return rc;
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    return frame_resize_args(fn, lay->h, lay->w, out_h, out_w, step, H, W);
+}
+
+static YuvLayout kernel_layout(const accel_yuv_layout& y)
+{
+    return {y.format, y.colour, y.h, y.w, y.pitch, y.pitch_c, y.u_offset, y.v_offset, y.frame_bytes};
+}
+
+extern "C" int accel_frame_yuv(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h, int out_w,
+                               double step, int H, int W, float* out)
+{
+    const char* fn = "accel_frame_yuv";
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_yuv: NULL argument");
+    if (int rc = frame_yuv_args(fn, yuv, n, layout, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ob = (size_t)n * 3 * H * W * 4;
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, yuv_bytes(n, *layout)));
+    float* d = static_cast<float*>(t.get(ob));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_frames_yuv(s, n, kernel_layout(*layout), means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_yuv_to_bgr(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch, int on_device)
+{
+    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: NULL argument");
+    if (int rc = yuv_layout_args("accel_yuv_to_bgr", yuv, n, layout, on_device ? yuv : nullptr)) return rc;
+    const int h = layout->h, w = layout->w;
+    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: bgr_out is NULL");
+    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
+        return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on_device) {
+        HIP_TRY(launch_yuv_to_bgr(yuv, n, kernel_layout(*layout), bgr_out, out_pitch, ctx->stream));
+        return 0;
+    }
+    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, yuv_bytes(n, *layout)));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_yuv_to_bgr: device allocation or upload failed");
+    HIP_TRY(launch_yuv_to_bgr(s, n, kernel_layout(*layout), d, (size_t)3 * w, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_model_write_yuv(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                                     int out_h, int out_w, double step, int H, int W, int src_on_device)
+{
+    const char* fn = "accel_model_write_yuv";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_yuv: NULL argument");
+    if (int rc = frame_yuv_args(fn, yuv, n, layout, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    const YuvLayout y = kernel_layout(*layout);
+    return write_frames(fn, m, buf, n, H, W, yuv, yuv_bytes(n, *layout), src_on_device, [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_yuv(src, n, y, means_bgr, out_h, out_w, step, H, W, dst, st);
+    });
+}
+
+// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow: bytes are bytes, P010's words among them)
+extern "C" int accel_model_commit_yuv(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
+                                      int out_w, double step, int H, int W)
+{
+    const char* fn = "accel_model_commit_yuv";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: unknown buffer '%s'", buf);
+    Shadow* sh = prefetched(m->shadows_u8, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_yuv_args(fn, sh->mem.ptr, n, layout, sh->mem.ptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    const size_t need = yuv_bytes(n, *layout);
+    if (need > sh->filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: (n - 1) x frame_bytes + the extent of a frame = %zu bytes, %zu were prefetched for '%s'",
+                    need, sh->filled, buf);
+    const YuvLayout y = kernel_layout(*layout);
+    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
+        return launch_frames_yuv(src, n, y, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
     });
 }
 

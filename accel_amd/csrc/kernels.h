@@ -161,6 +161,15 @@ hipError_t launch_frames_nv12(const unsigned char* src, int n, int h, int w, siz
                               const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* dst, hipStream_t st);
 hipError_t launch_nv12_to_bgr(const unsigned char* src, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
                               unsigned char* dst, size_t out_pitch, hipStream_t st);
+// I420, P010 and YUY2 frames (frames_yuv.hip): n frames in device memory laid out as `y` says (the fields of accel_yuv_layout, include/accel_hip.h:
+// format 0 I420, 1 P010, 2 YUY2; a field a format does not use is 0) -> the tensor launch_frames_u8 writes for the BGR frames
+// image.yuv_to_bgr_host makes of them, bit for bit -- and those BGR bytes themselves, rows `out_pitch` apart.  The 8-bit formats convert with
+// nv12_coefficients; yuv10_coefficients: the six integers of a colour mode for P010's 10-bit samples, or nullptr.
+struct YuvLayout { int format, colour, h, w; size_t pitch, pitch_c, u_offset, v_offset, frame_bytes; };
+const int32_t* yuv10_coefficients(int colour);
+hipError_t launch_frames_yuv(const unsigned char* src, int n, const YuvLayout& y, const double* means_bgr, int out_h, int out_w, double step,
+                             int H, int W, float* dst, hipStream_t st);
+hipError_t launch_yuv_to_bgr(const unsigned char* src, int n, const YuvLayout& y, unsigned char* dst, size_t out_pitch, hipStream_t st);
 // finished frames (results_u8.hip): n label maps of H x W bytes (valid region out_h x out_w, top left) taken to the source size h x w by the
 // integer nearest rule labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)] -- as labels (rows `dst_pitch` apart), as counts added
 // to an ncls x ncls matrix of 64-bit words (rows gt, columns prediction, ids >= ncls ignored; ncls <= 32), or as n x h x w x 3 colours

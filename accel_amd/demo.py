@@ -22,7 +22,7 @@ import numpy as np
 from . import mx
 from .config.config import config, update_config
 from .core.tester import Predictor, im_segment
-from .utils.image import NV12_COLOURS, bgr_to_nv12_host, resize, transform
+from .utils.image import NV12_COLOURS, YUV_FORMATS, bgr_to_nv12_host, bgr_to_yuv_host, resize, transform
 from .utils.tictoc import tic, toc
 
 
@@ -65,7 +65,7 @@ def get_symbols(version, cfg):
     return inst, inst.get_key_test_symbol(cfg), inst.get_cur_test_symbol(cfg)
 
 
-def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None):
+def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None, yuv=None, yuv_colour='bt709'):
     """demo.py:165-190: list of [data, data_key, feat_key] arrays per frame.
 
     One array per frame serves as this frame's `data` and as the next frame's `data_key` (the reference builds two
@@ -75,7 +75,9 @@ def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None):
     raw=True keeps every frame as its uint8 BGR bytes (mx.nd.raw_frames): no fp32 image is built on the host, a quarter of
     the bytes cross PCIe and the GPU resizes, removes the mean and pads (accel_model_write_u8).
     nv12=<colour mode> (utils.image.NV12_COLOURS) feeds every frame as NV12 bytes (mx.nd.nv12_frames), as a video decoder would hand it
-    out -- bgr_to_nv12_host stands in for the decoder; an eighth of the bytes cross PCIe and the GPU converts the colour as well."""
+    out -- bgr_to_nv12_host stands in for the decoder; an eighth of the bytes cross PCIe and the GPU converts the colour as well.
+    yuv=<format> (utils.image.YUV_FORMATS) feeds every frame as I420, P010 or YUY2 bytes (mx.nd.yuv_frames) converted with `yuv_colour`, the
+    same way -- bgr_to_yuv_host stands in for the decoder or the capture card."""
     data, prev = [], None
     ctx = mx.cpu_pinned() if pinned else None
     zero_feat = mx.nd.array(np.zeros((1, cfg.network.DFF_FEAT_DIM, 1, 1)))
@@ -85,6 +87,11 @@ def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None):
             if h % 2 or w % 2:
                 raise ValueError("--nv12: NV12 frames have an even height and width, this frame is %d x %d (odd-sized)" % (h, w))
             cur = mx.nd.nv12_frames(bgr_to_nv12_host(im, nv12), h, w, cfg, colour=nv12, ctx=ctx)
+        elif yuv is not None:
+            h, w = im.shape[:2]
+            if h % 2 or w % 2:
+                raise ValueError("--yuv: the %s frames made here have an even height and width, this frame is %d x %d (odd-sized)" % (yuv, h, w))
+            cur = mx.nd.yuv_frames(bgr_to_yuv_host(im, yuv, yuv_colour), yuv, h, w, cfg, colour=yuv_colour, ctx=ctx)
         elif raw:
             cur = mx.nd.raw_frames(im, cfg, ctx=ctx)
         else:
@@ -189,6 +196,11 @@ def main(argv=None):
                     help='feed the frames as NV12 bytes, the format video decoders hand out (implies --raw-frames): the frames, of even '
                          'height and width, are turned into NV12 on the host (standing in for a decoder) and the GPU converts the colour '
                          'with the named matrix, resizes, mean-subtracts and pads')
+    ap.add_argument('--yuv', default=None, choices=sorted(YUV_FORMATS),
+                    help='feed the frames as I420 (software decoders), P010 (10-bit hardware decoders) or YUY2 (capture cards) bytes (implies '
+                         '--raw-frames, excludes --nv12): the frames, of even height and width, are turned into that format on the host and '
+                         'the GPU converts the colour with the matrix of --yuv-colour, resizes, mean-subtracts and pads')
+    ap.add_argument('--yuv-colour', dest='yuv_colour', default='bt709', choices=sorted(NV12_COLOURS), help='the colour mode of --yuv')
     ap.add_argument('--finish-on-gpu', dest='finish_on_gpu', action='store_true',
                     help='finish every frame on the GPU: the timed loop fetches the labels at the SOURCE frame\'s size (padding and '
                          'resize undone there), the confusion matrix of the mIoU accumulates in HBM and --out writes those labels; '
@@ -215,7 +227,9 @@ def main(argv=None):
         raise ValueError("--confidence needs --finish-on-gpu")
     if args.interpolate and not args.finish_on_gpu:
         raise ValueError("--interpolate needs --finish-on-gpu")
-    if args.nv12:
+    if args.nv12 and args.yuv:
+        raise ValueError("--nv12 and --yuv are mutually exclusive: the frames are fed in one format")
+    if args.nv12 or args.yuv:
         args.raw_frames = True
     if args.cfg:
         update_config(args.cfg)
@@ -248,6 +262,8 @@ def main(argv=None):
     H, W = frames[0].shape[:2]
     if args.nv12 and (H % 2 or W % 2):
         raise ValueError("--nv12: NV12 frames have an even height and width, these frames are %d x %d (odd-sized)" % (H, W))
+    if args.yuv and (H % 2 or W % 2):
+        raise ValueError("--yuv: the %s frames made here have an even height and width, these frames are %d x %d (odd-sized)" % (args.yuv, H, W))
     if args.finish_on_gpu:    # how a label map goes back to a frame: the valid region of the bound size and the frame's own size
         from .core import results
         from .utils.image import resize_geometry
@@ -267,7 +283,8 @@ def main(argv=None):
         print('no --params given: seeded random weights (throughput is valid, mIoU is meaningless)')
         arg_params, aux_params = synth.model_params(version, H, W, config)
 
-    data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames, nv12=args.nv12)
+    data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames, nv12=args.nv12, yuv=args.yuv,
+                         yuv_colour=args.yuv_colour)
     runner = ClipRunner(version, config, arg_params, aux_params, (H, W))
     for j in range(min(2, len(data))):       # warm up (demo.py:207-220)
         runner.step(j, data[j], interv)[1].asnumpy()

@@ -8,7 +8,7 @@ import types as _types
 from . import operator
 from . import symbol
 from . import symbol as sym
-from .ndarray import DataBatch, DeviceArray, NV12Frames, RawFrames, array, argmax, nv12_frames, raw_frames, zeros
+from .ndarray import DataBatch, DeviceArray, NV12Frames, RawFrames, YUVFrames, array, argmax, nv12_frames, raw_frames, yuv_frames, zeros
 
 contrib = _types.SimpleNamespace(
     symbol=_types.SimpleNamespace(DeformableConvolution=symbol.DeformableConvolution),
@@ -16,7 +16,7 @@ contrib = _types.SimpleNamespace(
 io = _types.SimpleNamespace(DataBatch=DataBatch)
 sym.split = symbol.split
 nd = _types.SimpleNamespace(array=array, argmax=argmax, zeros=zeros, NDArray=DeviceArray, raw_frames=raw_frames, RawFrames=RawFrames,
-                            nv12_frames=nv12_frames, NV12Frames=NV12Frames)
+                            nv12_frames=nv12_frames, NV12Frames=NV12Frames, yuv_frames=yuv_frames, YUVFrames=YUVFrames)
 ndarray = nd
 
 

@@ -194,6 +194,72 @@ def nv12_frames(buf, h, w, cfg, colour="bt601", pitch=None, uv_offset=None, ctx=
                       uv_offset=uv_offset, ctx=ctx)
 
 
+class YUVFrames(RawFrames):
+    """Video frames as a software decoder (I420 / YV12), a 10-bit hardware decoder (P010) or a capture card (YUY2) hands them out, standing for
+    the same image tensor as the RawFrames of their BGR conversion (utils.image.yuv_to_bgr_host): a Predictor uploads the BYTES -- 1.5, 3 or 2
+    per pixel -- and the GPU converts the colour, resizes, removes the mean and pads (accel_model_write_yuv / _prefetch_u8 / _commit_yuv).
+    `.yuv` holds the bytes (flat: n frames `frame_bytes` apart), `.layout` what the C ABI is told about them (utils.image.yuv_layout plus n and
+    colour); `.frames` is the BGR conversion computed on the host on first use, for consumers that want the picture (core.results), and
+    `.asnumpy()` the tensor computed from it."""
+
+    def __init__(self, buf, fmt, h, w, pixel_means, target_size, max_size, stride=0, colour="bt709", ctx=None, **layout):
+        from ..utils import image
+        if isinstance(buf, (list, tuple)):
+            if len({np.shape(f) for f in buf}) != 1 or len({np.asarray(f).dtype for f in buf}) != 1:
+                raise ValueError("all frames of one YUV array must have the same number of bytes")
+            buf = np.stack([np.asarray(f).reshape(-1) for f in buf])
+        if np.ndim(buf) == 2 and layout.get("frame_bytes") is None:
+            layout["frame_bytes"] = np.shape(buf)[1] * np.asarray(buf).dtype.itemsize
+        lay = image.yuv_layout(fmt, h, w, **layout)
+        a, n = image.yuv_bytes(buf, lay)
+        pb = None
+        if ctx is not None and getattr(ctx, "device_type", "") == "cpu_pinned":
+            from .. import runtime
+            pb = runtime.PinnedBuffer(a.shape, np.uint8)
+            pb.array[...] = a
+            yuv = pb.array
+        else:
+            yuv = np.array(a, order="C", copy=True)      # a copy, like mx.nd.array: later edits of the source do not reach it
+        yuv.setflags(write=False)
+        h, w = lay["h"], lay["w"]
+        scale, out_h, out_w, H, W = image.resize_geometry(h, w, target_size, max_size, stride)
+        DeviceArray.__init__(self, shape=(n, 3, H, W), fetch=self._host_tensor, pinned=pb)
+        self.yuv = yuv
+        self.layout = dict(n=n, colour=image.nv12_colour(colour), **lay)
+        self._frames = None
+        self.means = tuple(float(v) for v in np.asarray(pixel_means, np.float64).reshape(-1))
+        self.resize_args = (target_size, max_size, stride)
+        self.scale = scale
+        self.geometry = dict(out_h=out_h, out_w=out_w, step=image.resample_step(h, w, scale, out_h, out_w), H=H, W=W)
+
+    @property
+    def frames(self):
+        """the frames as uint8 n x h x w x 3 BGR, converted on the host on first use"""
+        if self._frames is None:
+            from ..utils import image
+            lay = {k: v for k, v in self.layout.items() if k not in ("n", "colour", "format", "h", "w")}
+            f = image.yuv_to_bgr_host(self.yuv, self.layout["format"], self.layout["h"], self.layout["w"], colour=self.layout["colour"], **lay)
+            f.setflags(write=False)
+            self._frames = f
+        return self._frames
+
+    def __repr__(self):
+        from ..utils import image
+        name = sorted(image.YUV_FORMATS, key=image.YUV_FORMATS.get)[self.layout["format"]]
+        return "<YUVFrames %s %dx%dx%d for %s>" % (name, self.layout["n"], self.layout["h"], self.layout["w"], "x".join(map(str, self._shape)))
+
+
+def yuv_frames(buf, fmt, h, w, cfg, colour="bt709", pitch=None, pitch_c=None, u_offset=None, v_offset=None, frame_bytes=None, ctx=None):
+    """I420, P010 or YUY2 frames (`fmt`: utils.image.YUV_FORMATS) of h x w pixels for a Predictor -- uint8 bytes (uint16 words too for P010): one
+    flat frame, n x frame_bytes, a flat run of frames, or a list of frames -- converted with `colour` (utils.image.NV12_COLOURS), resized to
+    cfg.SCALES[0], centred on cfg.network.PIXEL_MEANS and padded to cfg.network.IMAGE_STRIDE on the GPU.  The layout keywords are those of
+    utils.image.yuv_layout (tightly packed where nothing is given; the bytes from frame to frame default to the row length of an
+    n x frame_bytes buffer).  Always a COPY of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
+    target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
+    return YUVFrames(buf, fmt, h, w, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, colour=colour, ctx=ctx, pitch=pitch,
+                     pitch_c=pitch_c, u_offset=u_offset, v_offset=v_offset, frame_bytes=frame_bytes)
+
+
 def zeros(shape, ctx=None, dtype=np.float32):
     return DeviceArray(host=np.zeros(shape, dtype))
 

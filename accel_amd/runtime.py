@@ -35,6 +35,12 @@ def build(force=False):
     return LIB_PATH
 
 
+class YUVLayout(ctypes.Structure):
+    """accel_yuv_layout (include/accel_hip.h): how I420 (0), P010 (1) or YUY2 (2) frames lie in memory, and their colour mode"""
+    _fields_ = [("format", ctypes.c_int), ("colour", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("pitch", ctypes.c_size_t),
+                ("pitch_c", ctypes.c_size_t), ("u_offset", ctypes.c_size_t), ("v_offset", ctypes.c_size_t), ("frame_bytes", ctypes.c_size_t)]
+
+
 def _declare(lib):
     c = ctypes
     vp, i, f, sz = c.c_void_p, c.c_int, c.c_float, c.c_size_t
@@ -82,6 +88,11 @@ def _declare(lib):
         "accel_nv12_to_bgr": [vp, vp, i, i, i, sz, sz, sz, i, vp, sz, i],
         "accel_model_write_nv12": [vp, c.c_char_p, vp, i, i, i, sz, sz, sz, i, vp, i, i, c.c_double, i, i, i],
         "accel_model_commit_nv12": [vp, c.c_char_p, i, i, i, sz, sz, sz, i, vp, i, i, c.c_double, i, i],
+        "accel_yuv10_coefficients": [i, c.POINTER(c.c_int32)],
+        "accel_frame_yuv": [vp, vp, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, vp],
+        "accel_yuv_to_bgr": [vp, vp, i, c.POINTER(YUVLayout), vp, sz, i],
+        "accel_model_write_yuv": [vp, c.c_char_p, vp, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, i],
+        "accel_model_commit_yuv": [vp, c.c_char_p, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i],
         "accel_labels_to_source": [vp, vp, i, i, i, i, i, i, i, vp, sz],
         "accel_labels_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, vp],
         "accel_labels_colour": [vp, vp, i, i, i, i, i, i, i, vp, i, vp, sz, i, vp, sz],
@@ -210,6 +221,30 @@ def nv12_coefficients(colour):
     """accel_nv12_coefficients: the six integers (yoff, ky, krv, kgu, kgv, kbu) of colour mode 0 .. 3 as the library holds them (no GPU)"""
     out = (ctypes.c_int32 * 6)()
     check(lib().accel_nv12_coefficients(int(colour), out))
+    return tuple(int(v) for v in out)
+
+
+def yuv_struct(layout, colour=None):
+    """the YUVLayout of a utils.image.yuv_layout dict (`colour`, a name or a number, unless the dict holds one)"""
+    from .utils import image
+    colour = layout.get("colour", 0) if colour is None else colour
+    return YUVLayout(int(layout["format"]), image.nv12_colour(colour), int(layout["h"]), int(layout["w"]), int(layout["pitch"]),
+                     int(layout["pitch_c"]), int(layout["u_offset"]), int(layout["v_offset"]), int(layout["frame_bytes"]))
+
+
+def _yuv_frames(buf, fmt, h, w, colour=0, **layout):
+    """I420 / P010 / YUY2 bytes as the C ABI takes them: (contiguous flat uint8 array, n, YUVLayout); the keywords are those of
+    utils.image.yuv_layout"""
+    from .utils import image
+    lay = image.yuv_layout(fmt, h, w, **layout)
+    a, n = image.yuv_bytes(buf, lay)
+    return a, n, yuv_struct(lay, colour)
+
+
+def yuv10_coefficients(colour):
+    """accel_yuv10_coefficients: the six integers (yoff, ky, krv, kgu, kgv, kbu) of colour mode 0 .. 3 for P010's 10-bit samples (no GPU)"""
+    out = (ctypes.c_int32 * 6)()
+    check(lib().accel_yuv10_coefficients(int(colour), out))
     return tuple(int(v) for v in out)
 
 
@@ -400,6 +435,29 @@ class Context(object):
         context's stream; the caller keeps the source unchanged until the kernel has run"""
         check(lib().accel_nv12_to_bgr(self.handle, ctypes.c_void_p(src_ptr), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
                                       int(colour), ctypes.c_void_p(dst_ptr), int(out_pitch), 1))
+
+    def frame_yuv(self, buf, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, **layout):
+        """accel_frame_yuv: I420 / P010 / YUY2 bytes (see utils.image.yuv_layout for the layout keywords, yuv_bytes for the buffer) -> the
+        n x 3 x H x W fp32 tensor transform(resize(yuv_to_bgr_host(..))) gives on the host"""
+        a, n, lay = _yuv_frames(buf, fmt, h, w, colour, **layout)
+        out = np.empty((n, 3, int(H), int(W)), np.float32)
+        check(lib().accel_frame_yuv(self.handle, _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W),
+                                    _fp(out)))
+        return out
+
+    def yuv_to_bgr(self, buf, fmt, h, w, colour=0, out=None, **layout):
+        """accel_yuv_to_bgr: I420 / P010 / YUY2 bytes -> n x h x w x 3 uint8 BGR (utils.image.yuv_to_bgr_host, on the GPU); `out`: n x h x pitch
+        bytes to write the rows into instead"""
+        a, n, lay = _yuv_frames(buf, fmt, h, w, colour, **layout)
+        out, out_pitch = _result_rows(out, n, lay.h, lay.w, 3)
+        check(lib().accel_yuv_to_bgr(self.handle, _fp(a), n, ctypes.byref(lay), _fp(out), out_pitch, 0))
+        return out
+
+    def yuv_to_bgr_device(self, src_ptr, dst_ptr, n, layout, out_pitch, colour=None):
+        """the same from HBM into HBM (`layout`: a utils.image.yuv_layout dict or a YUVLayout): only enqueued on the context's stream; the caller
+        keeps the source unchanged until the kernel has run"""
+        lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
+        check(lib().accel_yuv_to_bgr(self.handle, ctypes.c_void_p(src_ptr), int(n), ctypes.byref(lay), ctypes.c_void_p(dst_ptr), int(out_pitch), 1))
 
     def labels_to_source(self, labels, out_h, out_w, h, w, out=None):
         """accel_labels_to_source: n x H x W label maps whose valid region is out_h x out_w -> n x h x w labels at the source size
@@ -740,6 +798,29 @@ class Model(object):
         self.__dict__.get("_resident", {}).pop(buf, None)
         check(lib().accel_model_commit_nv12(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
                                             int(colour), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W)))
+
+    def write_yuv(self, buf, yuv, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, **layout):
+        """accel_model_write_yuv: host I420 / P010 / YUY2 bytes (see Context.frame_yuv) converted on the GPU into the image input `buf`"""
+        a, n, lay = _yuv_frames(yuv, fmt, h, w, colour, **layout)
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_yuv(self.handle, buf.encode(), _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
+                                          float(step), int(H), int(W), 0))
+
+    def write_yuv_device(self, buf, dev_ptr, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None):
+        """the same with the bytes already in HBM (`layout`: a utils.image.yuv_layout dict or a YUVLayout): read in place; the caller keeps
+        them unchanged until the kernel has run"""
+        lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_write_yuv(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), ctypes.byref(lay), _means3(means_bgr),
+                                          int(out_h), int(out_w), float(step), int(H), int(W), 1))
+
+    def commit_yuv(self, buf, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None):
+        """accel_model_commit_yuv: the compute stream waits for prefetch_u8 (the bytes go through the uint8 shadow), then the kernel converts
+        the shadow into `buf`"""
+        lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
+        self.__dict__.get("_resident", {}).pop(buf, None)
+        check(lib().accel_model_commit_yuv(self.handle, buf.encode(), int(n), ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
+                                           float(step), int(H), int(W)))
 
     # ---- finished frames: they only READ `labels` (no generation changes) ------------------------------------------------------
     def labels_to_source(self, n, out_h, out_w, h, w, out=None):

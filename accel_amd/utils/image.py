@@ -365,3 +365,186 @@ def bgr_to_nv12_host(frames, colour=0):
     out[:, :h * w] = q(yoff + y / ky).reshape(n, h * w)
     out[:, h * w:] = np.stack([q(cb), q(cr)], axis=-1).reshape(n, h * w // 2)
     return out
+
+
+# ---- I420, P010 and YUY2 frames -----------------------------------------------------------------------------------------------------------------
+# What a software decoder (I420; YV12 is I420 with the chroma planes in the other order), a 10-bit hardware decoder (P010) and a capture card
+# or USB camera (YUY2) hand out.  Frame i starts at byte i * frame_bytes; chroma is replicated, as on the NV12 route.
+#   I420   h rows of w luma bytes `pitch` apart from byte 0; the Cb plane at `u_offset` and the Cr plane at `v_offset`, each h/2 rows of w/2 bytes
+#          `pitch_c` apart; pixel (x, y) takes chroma at (x >> 1, y >> 1); h, w even.  The chroma planes start at or after h * pitch and need
+#          not be disjoint from each other (rows interleaved: pitch_c == pitch, v_offset == u_offset + pitch / 2)
+#   YUY2   h rows `pitch` (>= 2 w) apart of Y0 Cb Y1 Cr quads; pixel (x, y) takes the chroma of quad x >> 1 of its own row; w even, h >= 1
+#   P010   NV12's shape in little-endian 16-bit words: rows `pitch` (>= 2 w) bytes apart, a (Cb, Cr) word-pair plane at `u_offset`; the sample
+#          is word >> 6, the low six bits are never looked at; h, w even; pitch, u_offset and frame_bytes are multiples of 2
+YUV_FORMATS = {"i420": 0, "p010": 1, "yuy2": 2}
+
+
+def yuv_format(fmt):
+    """the number 0 .. 2 of a format given by name (YUV_FORMATS) or by number"""
+    if isinstance(fmt, str):
+        if fmt.lower() not in YUV_FORMATS:
+            raise ValueError("format = %r, must be one of %s" % (fmt, ", ".join(sorted(YUV_FORMATS))))
+        return YUV_FORMATS[fmt.lower()]
+    if isinstance(fmt, (int, np.integer)) and not isinstance(fmt, bool) and 0 <= int(fmt) <= 2:
+        return int(fmt)
+    raise ValueError("format = %r, must be in 0 .. 2 or one of %s" % (fmt, ", ".join(sorted(YUV_FORMATS))))
+
+
+def yuv_extent(layout):
+    """the bytes one frame of a yuv_layout occupies: one past the last byte of the last row of its last plane"""
+    f, h, w, pitch = layout["format"], layout["h"], layout["w"], layout["pitch"]
+    if f == 0:
+        return max(layout["u_offset"], layout["v_offset"]) + (h // 2 - 1) * layout["pitch_c"] + w // 2
+    if f == 1:
+        return layout["u_offset"] + (h // 2 - 1) * pitch + 2 * w
+    return (h - 1) * pitch + 2 * w
+
+
+def yuv_layout(fmt, h, w, pitch=None, pitch_c=None, u_offset=None, v_offset=None, frame_bytes=None):
+    """The accel_yuv_layout the C ABI takes (format, h, w, pitch, pitch_c, u_offset, v_offset, frame_bytes), checked as the C ABI checks it.
+    Tightly packed where nothing is given: pitch = a row (w bytes; 2 w for P010 and YUY2), I420's pitch_c = (pitch + 1) // 2, the Cb plane (the
+    chroma plane of P010) right behind the luma plane, I420's Cr plane right behind its Cb plane, the next frame right behind the last byte of
+    this one (yuv_extent).  A field the format does not use is 0, and giving it another value is an error."""
+    f = yuv_format(fmt)
+    name = sorted(YUV_FORMATS, key=YUV_FORMATS.get)[f].upper()
+    h, w = int(h), int(w)
+    even_h = f != 2
+    if h < 1 or h > 32768 or (even_h and h % 2):
+        raise ValueError("h = %d, must be %sin 1 .. 32768 for %s" % (h, "even and " if even_h else "", name))
+    if w < 1 or w > 32768 or w % 2:
+        raise ValueError("w = %d, must be even and in 1 .. 32768 for %s" % (w, name))
+    row = w if f == 0 else 2 * w
+    pitch = row if pitch is None else int(pitch)
+    if pitch < row:
+        raise ValueError("pitch = %d bytes, a row of w = %d %s pixels has %d" % (pitch, w, name, row))
+    if f == 0:
+        pitch_c = (pitch + 1) // 2 if pitch_c is None else int(pitch_c)
+        if pitch_c < w // 2:
+            raise ValueError("pitch_c = %d bytes, a chroma row of w = %d I420 pixels has %d" % (pitch_c, w, w // 2))
+        u_offset = h * pitch if u_offset is None else int(u_offset)
+        v_offset = u_offset + (h // 2) * pitch_c if v_offset is None else int(v_offset)
+    else:
+        for field, value in (("pitch_c", pitch_c), ("v_offset", v_offset)) + ((("u_offset", u_offset),) if f == 2 else ()):
+            if value is not None and int(value) != 0:
+                raise ValueError("%s = %d, but %s has no such field: it must be 0" % (field, int(value), name))
+        pitch_c = v_offset = 0
+        u_offset = 0 if f == 2 else (h * pitch if u_offset is None else int(u_offset))
+    for field, value in (("u_offset", u_offset), ("v_offset", v_offset))[:(2, 1, 0)[f]]:
+        if value < h * pitch:
+            raise ValueError("%s = %d bytes, the luma plane ends at %d" % (field, value, h * pitch))
+    lay = dict(format=f, h=h, w=w, pitch=pitch, pitch_c=pitch_c, u_offset=u_offset, v_offset=v_offset, frame_bytes=0)
+    end = yuv_extent(lay)
+    lay["frame_bytes"] = end if frame_bytes is None else int(frame_bytes)
+    if lay["frame_bytes"] < end:
+        raise ValueError("frame_bytes = %d, the last plane of a frame ends at %d" % (lay["frame_bytes"], end))
+    if f == 1:
+        for field in ("pitch", "u_offset", "frame_bytes"):
+            if lay[field] % 2:
+                raise ValueError("%s = %d, P010 words are 2-byte aligned: it must be even" % (field, lay[field]))
+    return lay
+
+
+def yuv_bytes(buf, layout):
+    """`buf` as (flat uint8 array, n): n frames laid out `frame_bytes` apart.  uint8, flat or n x frame_bytes; a flat buffer may end with the last
+    byte of its last frame ((n - 1) * frame_bytes + yuv_extent bytes).  uint16 is accepted for P010 and viewed as little-endian bytes."""
+    a = np.asarray(buf)
+    if a.dtype == np.uint16 and layout["format"] == 1:
+        a = np.ascontiguousarray(np.atleast_1d(a).astype("<u2", copy=False)).view(np.uint8)
+    if a.dtype != np.uint8:
+        raise ValueError("frame bytes must be uint8%s, got %s" % (" or uint16" if layout["format"] == 1 else "", a.dtype))
+    fb, end = layout["frame_bytes"], yuv_extent(layout)
+    if a.ndim == 2 and a.shape[0] >= 1 and a.shape[1] == fb:
+        return np.ascontiguousarray(a).reshape(-1), a.shape[0]
+    n = (a.size - end) // fb + 1 if a.size >= end else 0
+    if a.ndim != 1 or n < 1 or a.size > n * fb:
+        raise ValueError("frame bytes must be n x frame_bytes = n x %d, or flat: (n - 1) x %d + %d .. n x %d bytes; got shape %s"
+                         % (fb, fb, end, fb, a.shape))
+    return np.ascontiguousarray(a), n
+
+
+def yuv10_matrix(colour):
+    """the standard's float64 values at 10 bits (yoff10, ky, krv, kgu, kgv, kbu) that take (Y10 - yoff10, Cb10 - 512, Cr10 - 512) to R, G, B on the
+    0 .. 255 scale: the limited-range signal is 4 times the 8-bit one (nv12_matrix / 4), full range maps 1023 to 255 (nv12_matrix x 255 / 1023)"""
+    m = nv12_matrix(colour)
+    s = 0.25 if nv12_colour(colour) in (0, 2) else 255.0 / 1023.0
+    return (4 * m[0],) + tuple(v * s for v in m[1:])
+
+
+def yuv10_coefficients(colour):
+    """(yoff, ky, krv, kgu, kgv, kbu) of P010's integer rule, what accel_yuv10_coefficients returns: with c = Y10 - 4 * yoff, d = Cb10 - 512,
+    e = Cr10 - 512, R = clip((ky c + krv e + (1 << 17)) >> 18) and G, B alike.  Limited range (modes 0, 2): the integers of nv12_coefficients;
+    full range (1, 3): round(65536 x the standard's value x 1020 / 1023) -- 1023, not 1020, is white."""
+    if nv12_colour(colour) in (0, 2):
+        return nv12_coefficients(colour)
+    m = nv12_matrix(colour)
+    return (m[0],) + tuple(int(round(65536.0 * v * 1020.0 / 1023.0)) for v in m[1:])
+
+
+def yuv10_to_bgr(y, cb, cr, colour=0):
+    """P010's integer rule, the specification of csrc/frames_yuv.hip for 10-bit samples: arrays of Y10, Cb10, Cr10 -> (B, G, R) uint8 arrays"""
+    yoff, ky, krv, kgu, kgv, kbu = yuv10_coefficients(colour)
+    c = ky * (np.asarray(y).astype(np.int32) - 4 * yoff) + (1 << 17)
+    d = np.asarray(cb).astype(np.int32) - 512
+    e = np.asarray(cr).astype(np.int32) - 512
+    clip = lambda v: np.clip(v >> 18, 0, 255).astype(np.uint8)
+    return clip(c + kbu * d), clip(c - kgu * d - kgv * e), clip(c + krv * e)
+
+
+def yuv_to_bgr_host(buf, fmt, h, w, colour=0, **layout):
+    """The specification of accel_yuv_to_bgr, and with resize + transform behind it of accel_frame_yuv: I420, P010 or YUY2 bytes (see yuv_bytes;
+    the layout keywords are those of yuv_layout) -> n x h x w x 3 uint8 BGR.  Every sample is fetched from its own byte address, so planes may
+    interleave or overlap as the layout says; bytes in the gaps are not interpreted.  8-bit samples go through yuv_to_bgr, P010's word >> 6
+    through yuv10_to_bgr."""
+    lay = yuv_layout(fmt, h, w, **layout)
+    a, n = yuv_bytes(buf, lay)
+    f, h, w, pitch = lay["format"], lay["h"], lay["w"], lay["pitch"]
+    base = (np.arange(n, dtype=np.int64) * lay["frame_bytes"])[:, None, None]
+    ys, xs = np.arange(h, dtype=np.int64)[None, :, None], np.arange(w, dtype=np.int64)[None, None, :]
+    if f == 0:
+        c = base + (ys >> 1) * lay["pitch_c"] + (xs >> 1)
+        bgr = yuv_to_bgr(a[base + ys * pitch + xs], a[lay["u_offset"] + c], a[lay["v_offset"] + c], colour)
+    elif f == 2:
+        quad = base + ys * pitch + 4 * (xs >> 1)
+        bgr = yuv_to_bgr(a[base + ys * pitch + 2 * xs], a[quad + 1], a[quad + 3], colour)
+    else:
+        word = lambda i: (a[i].astype(np.int32) | a[i + 1].astype(np.int32) << 8) >> 6
+        uv = base + lay["u_offset"] + (ys >> 1) * pitch + 4 * (xs >> 1)
+        bgr = yuv10_to_bgr(word(base + ys * pitch + 2 * xs), word(uv), word(uv + 2), colour)
+    return np.ascontiguousarray(np.stack(bgr, axis=-1))
+
+
+def bgr_to_yuv_host(frames, fmt, colour=0):
+    """Tightly packed I420, P010 or YUY2 bytes (n x frame_bytes uint8) of uint8 BGR frames ([n x] h x w x 3, h and w even): the standard's forward
+    matrix in float64, chroma the mean of each 2 x 2 block (of each pair for YUY2), rint, clip; P010 samples sit in the top ten bits of their
+    words.  A tool for fabricating inputs (the demo's stand-in for a decoder), NOT the specification of anything on the GPU."""
+    fm = yuv_format(fmt)
+    f = np.asarray(frames)
+    if f.ndim == 3:
+        f = f[None]
+    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3:
+        raise ValueError("frames must be uint8 n x h x w x 3 (BGR), got %s %s" % (f.dtype, f.shape))
+    n, h, w = f.shape[:3]
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError("%s frames have an even height and width, got %d x %d" % (sorted(YUV_FORMATS, key=YUV_FORMATS.get)[fm].upper(), h, w))
+    kr, kg, kb, yoff, ky, s = _nv12_standard(colour)
+    b, g, r = (f[..., i].astype(np.float64) for i in range(3))
+    y = kr * r + kg * g + kb * b
+    block = (lambda p: p.reshape(n, h, w // 2, 2).mean(axis=3)) if fm == 2 else (lambda p: p.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4)))
+    luma = yoff + y / ky
+    cb = 128.0 + block((b - y) / (2.0 * (1.0 - kb))) / s
+    cr = 128.0 + block((r - y) / (2.0 * (1.0 - kr))) / s
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    if fm == 0:
+        return np.concatenate([q(luma).reshape(n, -1), q(cb).reshape(n, -1), q(cr).reshape(n, -1)], axis=1)
+    if fm == 2:
+        out = np.empty((n, h, w // 2, 4), np.uint8)
+        out[..., 0], out[..., 2] = q(luma[:, :, 0::2]), q(luma[:, :, 1::2])
+        out[..., 1], out[..., 3] = q(cb), q(cr)
+        return out.reshape(n, -1)
+    if yoff:        # limited range: the 10-bit signal is 4 times the 8-bit one
+        luma, cb, cr = 4.0 * luma, 4.0 * cb, 4.0 * cr
+    else:           # full range: 1023 is white, 512 is no chroma
+        luma, cb, cr = luma * (1023.0 / 255.0), 512.0 + (cb - 128.0) * (1023.0 / 255.0), 512.0 + (cr - 128.0) * (1023.0 / 255.0)
+    q10 = lambda p: (np.clip(np.rint(p), 0, 1023).astype("<u2") << 6)
+    words = np.concatenate([q10(luma).reshape(n, -1), np.stack([q10(cb), q10(cr)], axis=-1).reshape(n, -1)], axis=1)
+    return np.ascontiguousarray(words).view(np.uint8).reshape(n, -1)

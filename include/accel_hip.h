@@ -242,6 +242,50 @@ int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12,
 int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
                             const double* means_bgr, int out_h, int out_w, double step, int H, int W);
 
+/* ---- I420, P010 and YUY2 video frames -------------------------------------------------------------------------------
+ * What a software decoder (I420; YV12 is I420 with the chroma planes in the other order), a 10-bit hardware decoder
+ * (P010) and a capture card or USB camera (YUY2) hand out.  The bytes are uploaded as they are (1.5, 3 and 2 per pixel)
+ * and one kernel (csrc/frames_yuv.hip) converts the colour, resizes, removes the mean and pads: the tensor is, bit for
+ * bit, transform(resize(yuv_to_bgr_host(frame))) of accel_amd/utils/image.py.  The entry points mirror the NV12 ones
+ * argument for argument, with `n, const accel_yuv_layout*` in place of the flat layout:
+ *   format                0 I420, 1 P010, 2 YUY2
+ *   colour                as for NV12
+ *   h, w                  1 .. 32768; w even; h even for I420 and P010
+ *   pitch                 bytes from row to row of the luma plane (I420: >= w), of both planes (P010: >= 2 * w) or of the
+ *                         one plane (YUY2: >= 2 * w, rows of Y0 Cb Y1 Cr quads)
+ *   pitch_c               I420: bytes from row to row of each chroma plane (>= w / 2)
+ *   u_offset, v_offset    I420: the bytes of a frame at which its Cb and Cr planes begin, each h/2 rows of w/2 bytes; both
+ *                         >= h * pitch, in either order, and not required to be disjoint from each other (rows may interleave:
+ *                         pitch_c == pitch, v_offset == u_offset + pitch / 2).  P010: u_offset is where the h/2 rows of w/2
+ *                         (Cb, Cr) word pairs begin
+ *   frame_bytes           bytes from frame to frame, >= the extent of a frame: one past the last byte of the last row of
+ *                         its last plane.  n frames occupy (n - 1) * frame_bytes + extent bytes; a host buffer may end there
+ * A field the format does not use (pitch_c and v_offset for P010 and YUY2, u_offset for YUY2) must be 0.  P010 holds
+ * little-endian 16-bit words whose sample is word >> 6 (the low six bits are never looked at); its pitch, u_offset,
+ * frame_bytes and a device source address are multiples of 2.  Bytes in the gaps are never read.
+ * Chroma is replicated: I420 and P010 pixel (x, y) takes it at (x >> 1, y >> 1), YUY2 from quad x >> 1 of its own row.
+ * The 8-bit formats convert with the rule and the integers of NV12.  P010, with c = Y10 - 4 * yoff, d = Cb10 - 512,
+ * e = Cr10 - 512 in int32:
+ *     R = clip((ky*c + krv*e         + (1 << 17)) >> 18, 0, 255)
+ *     G = clip((ky*c - kgu*d - kgv*e + (1 << 17)) >> 18, 0, 255)
+ *     B = clip((ky*c + kbu*d         + (1 << 17)) >> 18, 0, 255)
+ * with NV12's integers for the limited-range modes and round(65536 x the standard's value x 1020 / 1023) for the
+ * full-range ones (1023 is white).  The output is 8-bit BGR; from there on nothing differs from the other routes.
+ * Argument errors return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_yuv10_coefficients  the six integers (yoff, ky, krv, kgu, kgv, kbu) of a colour mode for P010; host only
+ *   accel_frame_yuv, accel_yuv_to_bgr, accel_model_write_yuv, accel_model_commit_yuv
+ *                             as their NV12 namesakes; the bytes a commit converts were uploaded by
+ *                             accel_model_prefetch_u8 (P010's words travel as bytes) */
+typedef struct { int format, colour, h, w; size_t pitch, pitch_c, u_offset, v_offset, frame_bytes; } accel_yuv_layout;
+int accel_yuv10_coefficients(int colour, int32_t out[6]);
+int accel_frame_yuv(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                    int out_h, int out_w, double step, int H, int W, float* out);
+int accel_yuv_to_bgr(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch, int on_device);
+int accel_model_write_yuv(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                          int out_h, int out_w, double step, int H, int W, int src_on_device);
+int accel_model_commit_yuv(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                           int out_h, int out_w, double step, int H, int W);
+
 /* ---- finished frames: labels at the source size, confusion matrix, colour image ------------------------------------
  * The output side of the loop (demo.py:245-266: `.asnumpy()` of the label map, fast_hist, the palette PNG) on the GPU
  * (csrc/results_u8.hip).  A label map is n x H x W uint8; its valid (unpadded) region is out_h x out_w in the top-left
