@@ -22,7 +22,14 @@ Kernel size, stride, padding and dilation of a case are each an int or an (h, w)
 the geometry sweep crosses the 26 shapes of GEOMETRY with the 22 rows of GEOMETRY_KERNELS: 572 pairs, of which 507 run, 50 must be
 refused (RULES: a K step of 64, the DMA ring's Cin % 32, conv_b3d's Cin % 16) and 15 are f16-mode requests the layer declines (padded
 Cin % 8: it stays fp32, GEOMETRY_DEMOTED) -- 11 % not run.  With the narrow kernel on the 11 anisotropic shapes, the split-K reduce on
-one deep anisotropic K and the refusals of the kernels that demand square geometry: GEOMETRY_RUN 524, GEOMETRY_REFUSED 57."""
+one deep anisotropic K and the refusals of the kernels that demand square geometry: GEOMETRY_RUN 524, GEOMETRY_REFUSED 57.
+
+The Winograd block sweep crosses the 13 shapes of WINO_GEOMETRY (all 3x3 / 1 / pad 1: what varies is how the map falls into blocks of
+tiles, the K loop and its split -- wino_blocks, wino_split and wino_slices restate the launchers and conv_plan_split) with the 7 rows
+of WINO_KERNELS (40 in fp32, 41-43 as bf16x3 and as fp16x2), once on the Gaussian operands of every other case and once on DYADIC
+operands (Case.dyadic, part of data_key: integer pixels in [-4, 4], weights in {-8, -4, 0, 4, 8}, integer bias and residual, no batch
+norm, leaky slope or second output), on which every intermediate of F(2x2, 3x3) in every form is an integer below 2^24 and the result
+has no tolerance: WINO_RUN 182, WINO_REFUSED 7 (an odd side, Cin off the K step, pad 0)."""
 import collections
 import functools
 import zlib
@@ -34,6 +41,7 @@ from plan_helpers import bn_params, conv64, deconv64, pair, r4
 
 U = 2.0 ** -24
 SLOPE = 0.1
+DYADIC_X = 4            # dyadic operand set: integer pixels in [-4, 4], weights in {-8, -4, 0, 4, 8}
 
 
 def f32(a):
@@ -57,14 +65,15 @@ class Case(object):
     dilation (each an int or an (h, w) pair), the epilogue ("bias", "bn", "res", "dual" joined by +) and what ops() must report."""
 
     def __init__(self, fam, tile, Cin=32, Cout=136, H=13, W=19, N=3, k=3, s=1, p=1, d=1, epi="", act=0, split="b3", f16=False, mode="conv",
-                 ksplit=False, narrow=None, odd=False, raises=False, auto=False):
+                 ksplit=False, narrow=None, odd=False, raises=False, auto=False, dyadic=False):
         self.fam, self.tile, self.Cin, self.Cout, self.H, self.W, self.N = fam, tile, Cin, Cout, H, W, N
         k, s, p, d = (v if np.ndim(v) == 0 else tuple(int(e) for e in v) for v in (k, s, p, d))      # hashable: part of data_key
         self.k, self.s, self.p, self.d, self.act, self.split, self.f16, self.mode = k, s, p, d, act, split, f16, mode
         self.epi = frozenset(t for t in epi.split("+") if t)
         assert self.epi <= {"bias", "bn", "res", "dual"}, epi
-        self.ksplit, self.narrow, self.odd, self.raises, self.auto = ksplit, narrow, odd, raises, auto
+        self.ksplit, self.narrow, self.odd, self.raises, self.auto, self.dyadic = ksplit, narrow, odd, raises, auto, dyadic
         assert not auto or (tile is None and not narrow)
+        assert not dyadic or (self.epi <= {"bias", "res"} and act in (0, 1) and mode == "conv")      # nothing that rounds
         (self.kh, self.kw), (self.sh, self.sw), (self.ph, self.pw), (self.dh, self.dw) = pair(k), pair(s), pair(p), pair(d)
         if mode == "deconv2x":
             self.Ho, self.Wo, self.K = 2 * H - odd, 2 * W - odd, 4 * Cin
@@ -77,20 +86,23 @@ class Case(object):
 
     @property
     def id(self):
-        return "%s-t%s-%s%s-n%d-%dx%d-%dx%d-%s%s-act%d-%s%s%s" % (
+        return "%s-t%s-%s%s-n%d-%dx%d-%dx%d-%s%s-act%d-%s%s%s%s" % (
             self.fam, "auto" if self.auto else "none" if self.tile is None else self.tile, "f16" if self.f16 else self.split,
             "" if self.mode == "conv" else "-" + self.mode, self.N, self.Cin, self.Cout, self.H, self.W,
             "k%ss%sp%sd%s" % (_g(self.k), _g(self.s), _g(self.p), _g(self.d)), "-odd" if self.odd else "", self.act,
-            "+".join(sorted(self.epi)) or "plain", "-splitk" if self.ksplit else "", "-refused" if self.raises else "")
+            "+".join(sorted(self.epi)) or "plain", "-splitk" if self.ksplit else "", "-dyadic" if self.dyadic else "",
+            "-refused" if self.raises else "")
 
     @property
     def data_key(self):
-        """cases with the same key share inputs, weights and epilogue constants (and so the float64 convolution)"""
-        return (self.mode, self.odd, self.Cin, self.Cout, self.H, self.W, self.N, self.k, self.s, self.p, self.d)
+        """cases with the same key share inputs, weights and epilogue constants (and so the float64 convolution); a dyadic case
+        (small-integer operands: WINO_GEOMETRY) has one element more, so every other key keeps its repr and its seed"""
+        key = (self.mode, self.odd, self.Cin, self.Cout, self.H, self.W, self.N, self.k, self.s, self.p, self.d)
+        return key + ("dyadic",) if self.dyadic else key
 
 
 def _case_of(key, **kw):
-    return Case("", 0, *key[2:], mode=key[0], odd=key[1], **kw)
+    return Case("", 0, *key[2:11], mode=key[0], odd=key[1], dyadic=len(key) > 11, **kw)
 
 
 # ---- the case table ---------------------------------------------------------------------------------------------------------------
@@ -305,14 +317,157 @@ def _geometry_cases():
 GEOMETRY_RUN, GEOMETRY_REFUSED, GEOMETRY_DEMOTED = _geometry_cases()
 
 
+# ---- the Winograd block sweep -------------------------------------------------------------------------------------------------------
+# The Winograd kernels take one filter geometry (3x3 / 1 / pad 1, even maps); what they can get wrong is the decomposition of the map
+# into blocks of tiles (2x2 output pixels each), the K loop and its split.  Both are restated here in plain Python.
+WINO_TILES = (40, 41, 42, 43)
+
+
+def wino_bhs(tile, TH):
+    """log2 of the block height of the rectangular forms:
+    conv_wino_b3.hip conv_wino_b3u_blocks: `const int s = TH >= 8 ? 3 : TH >= 4 ? 2 : 1;` (block = (1 << s) x (64 >> s) tiles)
+    conv_wino_b3s.hip conv_wino_b3s_blocks: `const int s = TH >= 4 ? 2 : 1;` (block = (1 << s) x (32 >> s) tiles)"""
+    return (3 if TH >= 8 else 2 if TH >= 4 else 1) if tile == 42 else (2 if TH >= 4 else 1)
+
+
+def wino_blocks(tile, H, W, N):
+    """(block height, block width, blocks per image or None, MT) in tiles, of an N x H x W map:
+    40 / 41 -- conv_wino.hip launch_conv_wino, conv_wino_b3.hip launch_conv_wino_b3: `p.wino_T = p.M / 4; p.MT = (p.wino_T + TT - 1) /
+    TT;` with TT = 64, the kernels' `const int tg = m0 + tl; ... const int n = tt / THW, rem = tt - n * THW; const int ty = rem / TW`:
+    64 consecutive tiles in (n, ty, tx) order, a block straddles rows and images;
+    42 / 43 -- conv_wino_b3u_blocks / conv_wino_b3s_blocks: `return n * ((TH + BH - 1) / BH) * ((TW + BW - 1) / BW);` and the kernels'
+    `const int BX = (TW + BWm) >> bws, BY = (TH + (1 << bhs) - 1) >> bhs; un = mt / (BX * BY);`: a block never leaves its image."""
+    TH, TW = H // 2, W // 2
+    if tile in (40, 41):
+        return 1, 64, None, (N * TH * TW + 63) // 64
+    BH = 1 << wino_bhs(tile, TH)
+    BW = (64 if tile == 42 else 32) // BH
+    per = ((TH + BH - 1) // BH) * ((TW + BW - 1) // BW)
+    return BH, BW, per, N * per
+
+
+def wino_rows(cout_store):
+    """conv_wino.hip `int conv_wino_rows(int cout_store) { return (cout_store + KK - 1) / KK * KK; }`, KK = 64"""
+    return (cout_store + 63) // 64 * 64
+
+
+def wino_nt(case):
+    """launch_conv_wino*: `p.NT = p.wino_rows / KK;`"""
+    return wino_rows(r4(case.Cout)) // 64
+
+
+def wino_kstep(tile):
+    """channels per K step: conv_wino.hip `constexpr int BKC = 8;`, conv_wino_b3.hip `BKC = 16`, conv_wino_b3s.hip `BKS = 16`"""
+    return 8 if tile == 40 else 16
+
+
+def wino_split(tile, case):
+    """(ksplit, kt_per_split) of conv_igemm.hip conv_plan_split's two Winograd branches with no split_target set:
+        if (p.no_split || p.narrow) return 0;
+        const long blocks = <MT> * (long)conv_wino_rows(p.Cout_store) / 64;         MT as wino_blocks
+        const int KT = p.Cin / 8 [40] or p.Cin / 16 [41-43], min_steps = 4;
+        if (blocks >= 256 || KT < 2 * min_steps) return 0;
+        int want = (int)((512 + blocks - 1) / blocks);
+        int ks = want < KT / min_steps ? want : KT / min_steps;
+        if (ks < 2) return 0;
+        p.kt_per_split = ((KT + ks - 1) / ks + 1) / 2 * 2 [40: even, the K loop is unrolled by 2] or (KT + ks - 1) / ks [41-43];
+        p.ksplit = (KT + p.kt_per_split - 1) / p.kt_per_split;
+        if (p.ksplit < 2) { p.ksplit = 1; p.kt_per_split = 0; return 0; }"""
+    if not case.ksplit:      # the plan line says nosplit=1
+        return 1, 0
+    blocks = wino_blocks(tile, case.H, case.W, case.N)[3] * wino_rows(r4(case.Cout)) // 64
+    KT = case.Cin // wino_kstep(tile)
+    if blocks >= 256 or KT < 8:
+        return 1, 0
+    ks = min((512 + blocks - 1) // blocks, KT // 4)
+    if ks < 2:
+        return 1, 0
+    per = (KT + ks - 1) // ks
+    if tile == 40:
+        per = (per + 1) // 2 * 2
+    ksplit = (KT + per - 1) // per
+    return (ksplit, per) if ksplit >= 2 else (1, 0)
+
+
+def wino_slices(tile, case):
+    """the K steps of every slice, as the kernels take them: `nk = p.ksplit > 1 ? min(p.kt_per_split, nk_all - kb) : nk_all`"""
+    KT = case.Cin // wino_kstep(tile)
+    ksplit, per = wino_split(tile, case)
+    return [KT] if ksplit == 1 else [min(per, KT - i * per) for i in range(ksplit)]
+
+
+# WINO_GEOMETRY: shapes only, all 3x3 / 1 / pad 1; TH x TW = H / 2 x W / 2 tiles.  Every block class of 42 (8x8 for TH >= 8, 4x16 for
+# 4 <= TH < 8, 2x32 below) and of 43 (4x8 for TH >= 4, 2x16 below) meets a map it fits exactly, one ragged in the tile rows alone, one
+# in the tile columns alone and one in both with a ONE-tile corner block (test_conv_ref_cpu.py asserts it, and the rest of what this
+# column says).  The epilogue rotates over the shapes with ROT.
+#        name          Cin Cout  H    W  N     what it is for
+_WG = [
+    ("onetile",         16,   5,  2,   2, 1),  # one tile; one K step on 41-43 (two on 40); Cout_store 8; nblk 1
+    ("strip",           32,  40,  2,  66, 3),  # TH 1: 2x32 / 2x16 with the lower tile row invalid, TW 33 = 32 + 1 = 16 + 16 + 1 (one-tile
+                                               # corner blocks); 42's raw patch copy at its largest; linear blocks straddle the images
+    ("th3w32",          48,  68,  6,  64, 2),  # two-row blocks ragged in the rows alone (the second has one valid row); three K steps;
+                                               # a second channel block with 4 channels in use
+    ("fit",             32,  64,  8,  32, 1),  # exact fit: 42 one 4x16 block, 43 two 4x8 blocks, 40 / 41 one block of 64 tiles; Cout 64
+    ("th5w17",          64,  72, 10,  34, 2),  # 4 + 1 tile rows, 16 + 1 and 8 + 8 + 1 tile columns (one-tile corners); four K steps
+    ("th2w32",          16, 132,  4,  64, 3),  # 2x32 (one block an image) and 2x16 exactly; Cout 2 x 64 + 4; linear blocks end with the image
+    ("th8",             32,  40, 16,  16, 2),  # 42 switches to 8x8, exactly one block an image; 43: two 4x8 blocks an image
+    ("th9w9",           80,  40, 18,  18, 1),  # 8x8 and 4x8 ragged by one both ways: the corner block holds ONE tile; five K steps;
+                                               # K = 720 > 576: the wino32 bar; a linear block covers more than seven tile rows
+    ("tall",            32,  40, 34,  16, 1),  # TH 17 = 2 x 8 + 1 = 4 x 4 + 1 with TW 8: 8x8 and 4x8 ragged in the rows alone
+    ("wide",            16,  40, 16, 130, 1),  # TW 65 = 8 x 8 + 1: 8x8 and 4x8 ragged in the columns alone, the last column one tile wide
+    ("deep",           512,  72,  4,   8, 2),  # nosplit=1: 32 (64 on 40) K steps in one slice; TH 2, TW 4: 2x32 / 2x16 ragged in the columns alone
+    ("split54",        144,  72,  8,   8, 1),  # split over K: 41-43 KT 9 -> 5 + 4, 40 KT 18 -> 6 + 6 + 6; 4x16 / 4x8 ragged in the columns alone
+    ("split_ragged",   176,  72, 14,  32, 2),  # split over K on blocks ragged in the rows (TH 7, the last 4-row class of 42): 41-43 KT 11
+                                               # -> 6 + 5, 40 KT 22 -> 6 + 6 + 6 + 4: a short last slice in every kernel
+]
+WINO_GEOMETRY = collections.OrderedDict((g[0], dict(zip(("Cin", "Cout", "H", "W", "N"), g[1:]))) for g in _WG)
+WINO_SPLIT_SHAPES = ("split54", "split_ragged")      # the only ones without nosplit=1
+# (family, id, ACCEL_SPLIT): 40 in fp32, 41-43 as bf16x3 and as fp16x2
+WINO_KERNELS = [("wino-geo-fp32", 40, "b3"), ("wino-geo-b3", 41, "b3"), ("wino-geo-b3", 42, "b3"), ("wino-geo-b3", 43, "b3"),
+                ("wino-geo-h2", 41, "h2"), ("wino-geo-h2", 42, "h2"), ("wino-geo-h2", 43, "h2")]
+# the epilogues of the dyadic operand set: nothing that rounds (no batch norm, no leaky slope, no second output)
+DYADIC_ROT = [("bias", 0), ("", 1), ("res", 1), ("res", 0)]
+
+
+def wino_case(name, fam, tile, split, dyadic=False, index=None):
+    i = list(WINO_GEOMETRY).index(name) if index is None else index
+    epi, act = (DYADIC_ROT if dyadic else ROT)[i % 4]
+    ksplit = name in WINO_SPLIT_SHAPES
+    return Case("wino-geo-splitk" if ksplit else fam, tile, epi=epi, act=act, split=split, ksplit=ksplit, dyadic=dyadic, **WINO_GEOMETRY[name])
+
+
+def _wino_cases():
+    run = [wino_case(name, fam, tile, split, dyadic) for dyadic in (False, True) for name in WINO_GEOMETRY for fam, tile, split in WINO_KERNELS]
+    # what conv_wino_eligible / conv_wino_b3_eligible rule out, on sub-views: an odd side, input channels off the K step, no padding
+    refused = [Case("wino-geo", 40, Cout=40, H=12, W=17, epi="bias", raises=True),
+               Case("wino-geo", 43, Cout=40, H=11, W=18, epi="bias", raises=True),
+               Case("wino-geo", 43, Cout=40, H=11, W=18, epi="bias", split="h2", raises=True),
+               Case("wino-geo", 41, Cin=24, Cout=40, H=12, W=18, epi="bias", raises=True),
+               Case("wino-geo", 40, Cin=8, Cout=40, H=12, W=18, epi="bias", raises=True),
+               Case("wino-geo", 40, Cout=40, H=12, W=18, p=0, epi="bias", raises=True),
+               Case("wino-geo", 42, Cout=40, H=12, W=18, p=0, epi="bias", raises=True)]
+    return run, refused
+
+
+WINO_RUN, WINO_REFUSED = _wino_cases()
+
+
 # ---- operands ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _operands(key):
-    mode, odd, Cin, Cout, H, W, N, k, s, p, d = key
+    mode, odd, Cin, Cout, H, W, N, k, s, p, d = key[:11]
     c = _case_of(key)
     rng = np.random.default_rng(zlib.crc32(repr(key).encode()))
     o = {}
-    if mode == "cols":
+    if c.dyadic:
+        # integers all the way: every intermediate of F(2x2, 3x3) (G g G^T of multiples of 4, B^T d B, the sums over the channels,
+        # A^T m A), every term of a split operand and the epilogue are integers far below 2^24 -- an evaluation in ANY order is exact
+        o["x"] = f32(rng.integers(-DYADIC_X, DYADIC_X + 1, (N, Cin, H, W)))
+        o["w"] = f32(4 * rng.integers(-2, 3, (Cout, Cin, c.kh, c.kw)))
+        o["res"] = f32(rng.integers(-64, 65, (N, Cout, c.Ho, c.Wo)))
+        o["bias"] = f32(rng.integers(-16, 17, Cout))
+        o["bn"] = o["bn2"] = {}
+    elif mode == "cols":
         o["x"] = f32(rng.standard_normal((N, 9 * Cin, H, W)))          # the column buffer [pixel][tap][c] as NCHW planes
         o["w"] = f32(rng.standard_normal((Cout, Cin, 3, 3)) / np.sqrt(c.K))
     elif mode == "deconv2x":
@@ -321,10 +476,11 @@ def _operands(key):
     else:
         o["x"] = f32(rng.standard_normal((N, Cin, H, W)))
         o["w"] = f32(rng.standard_normal((Cout, Cin, c.kh, c.kw)) / np.sqrt(c.K))
-    o["res"] = f32(rng.standard_normal((N, Cout, c.Ho, c.Wo)))
-    o["bias"] = f32(rng.standard_normal(Cout) * 0.5)
-    o["bn"] = bn_params(rng, "bn", Cout, Cout - 1)
-    o["bn2"] = bn_params(rng, "bn2", Cout, Cout - 1, negative=True)
+    if not c.dyadic:
+        o["res"] = f32(rng.standard_normal((N, Cout, c.Ho, c.Wo)))
+        o["bias"] = f32(rng.standard_normal(Cout) * 0.5)
+        o["bn"] = bn_params(rng, "bn", Cout, Cout - 1)
+        o["bn2"] = bn_params(rng, "bn2", Cout, Cout - 1, negative=True)
     for a in o.values():
         if isinstance(a, np.ndarray):
             a.setflags(write=False)

@@ -21,7 +21,7 @@ Every test prints its largest error-to-bound ratio (Winograd: error to bar; run 
 family.  One run on an MI355X: igemm 0-4 / 5-9 / 31-35 0.100, 10-12 + 14 0.078, 13 / 15 0.083, 16-19 0.078; bf16x3 and fp16x2 forms
 0.014; Winograd fp32 0.077, bf16x3 0.066, fp16x2 0.073, split over K 0.081, behind the deep-K reduce 0.092; weight-stationary 0.065;
 halo 0.002; narrow 0.036; split-K reduce below 0.001; deconvolution 0.034; column GEMM 0.009; f16 mode 0.054 (the stem cases of that
-run failed: see conv_stem.hip's output stores).  The whole file took 3 s.
+run failed: see conv_stem.hip's output stores; 0.027 in the run of the sweeps below).  The whole file took 3 s.
 
 The geometry sweep (test_conv_geometry_on_sub_views) runs the same six assertions on conv_ref.GEOMETRY_RUN: 26 small shapes -- kernel
 size, stride, padding and dilation with unequal height and width members (each pair on its own, and all four on a non-square map),
@@ -31,8 +31,19 @@ at and one above the pixel tiles, Cout 5 / 33 / 129 / 260 -- crossed with one la
 conv_igemm_f16 0, 10, conv_b3r 76 and conv_b3d 82, 84, 88) and with no tile= at all under both split settings (the id conv_pick_tile
 reports must be part of the build), plus the narrow pixel kernel on the anisotropic shapes and the split-K reduce behind 0 and 76
 on one deep anisotropic K: 524 cases.  57 more must be refused (conv_ref.RULES and the kernels that demand square geometry), and 15
-f16-mode requests on layers with a padded Cin off a multiple of 8 must report an fp32 layer.  The sweep has not been run on an
-MI355X yet (none could be had when it was written): its ratios per family (geo-*) are printed by the last test and belong here."""
+f16-mode requests on layers with a padded Cin off a multiple of 8 must report an fp32 layer.  One run on an MI355X, largest
+error-to-bound ratio per family: geo-igemm 0.195, geo-b3 0.221, geo-b3r-b3 0.221, geo-b3r-h2 0.297, geo-f16 / geo-f16-b3r /
+geo-f16-b3d 0.034, geo-auto 0.195, geo-narrow 0.223, geo-splitk 0.001.
+
+The Winograd block sweep (test_winograd_blocks_on_sub_views) runs them on conv_ref.WINO_RUN: the 13 shapes of WINO_GEOMETRY -- every
+block class of 42 (8x8, 4x16, 2x32) and 43 (4x8, 2x16) on a map it fits, on maps ragged in the tile rows, in the tile columns and in
+both with a one-tile corner block; linear blocks of 40 / 41 below, at and above 64 tiles, across rows and images; K loops of 1, 2, 3,
+4, 5 and 32 steps (2 to 64 on 40); splits over K with equal slices and with a short last one; nblk below 8, a multiple of 8 and
+neither; Cout_store 8, 64, 68 and 132 -- crossed with 40 in fp32 and 41-43 as bf16x3 and as fp16x2, on Gaussian operands (assertion 5
+against conv_ref.bar) and on dyadic ones, where assertion 5 is equality of every word of y with the float64 reference rounded once:
+182 cases, 7 more refused.  ops() must report the forced id and the ksplit of conv_ref.wino_split.  The same run, error to bar:
+wino-geo-fp32 0.171, wino-geo-b3 0.171, wino-geo-h2 0.081, wino-geo-splitk 0.100; all 91 dyadic cases bit for bit.  The whole file
+(1010 tests) took 9 s; the 182 cases of this sweep with the 71 refusals, in a process of their own, 6 s."""
 import collections
 
 import numpy as np
@@ -148,6 +159,8 @@ def on_sub_views(ctx, monkeypatch, case):
             if case.tile is not None:
                 assert op["tile"] == case.tile, op
             assert (op["ksplit"] > 1) == case.ksplit, op
+            if case.fam.startswith("wino-geo"):      # the K split is the one conv_ref restates: its slices are what the table is built on
+                assert op["ksplit"] == R.wino_split(case.tile, case)[0], (op, R.wino_split(case.tile, case))
         if case.narrow:
             M = case.N * case.Ho * case.Wo
             strip = (pair(case.k), pair(case.s), pair(case.d), pair(case.p)) == ((3, 3), (1, 1), (1, 1), (1, 1)) and case.Cout <= 2
@@ -191,6 +204,11 @@ def on_sub_views(ctx, monkeypatch, case):
             s, src = r1["c"]
             assert src == 2 and s == H2.range_scale(H2.float_bits(np.abs(o["x"]).max())), (s, src)
         ratio = R.check(case, got["Y"], got.get("Y2"))      # 5
+        if case.dyadic:      # integers in every intermediate of every form: no tolerance, the float64 reference rounded once
+            want = R.reference(case).y.astype(np.float32)
+            wrong = np.argwhere(got["Y"].view(np.uint32) != want.view(np.uint32))
+            assert not len(wrong), "%s: %d words differ from the exact result, the first at (n, c, y, x) = %s: %r for %r" % (
+                case.id, len(wrong), tuple(wrong[0]), got["Y"][tuple(wrong[0])], want[tuple(wrong[0])])
         WORST[case.fam] = max(WORST[case.fam], ratio)
         print("%s: at %.3f of the %s" % (case.id, ratio, "bar" if case.wino else "bound"))
 
@@ -217,7 +235,15 @@ def test_conv_geometry_on_sub_views(ctx, monkeypatch, case):
     on_sub_views(ctx, monkeypatch, case)
 
 
-@pytest.mark.parametrize("case", R.REFUSED + R.GEOMETRY_REFUSED, ids=lambda c: c.id)
+@pytest.mark.parametrize("case", R.WINO_RUN, ids=lambda c: c.id)
+def test_winograd_blocks_on_sub_views(ctx, monkeypatch, case):
+    """the Winograd block sweep (conv_ref.WINO_GEOMETRY x WINO_KERNELS, on Gaussian and on dyadic operands): every block class of 42
+    and 43 fitting and ragged, linear blocks across rows and images, K loops of one step to 64, short last slices of a split over K,
+    every branch of the XCD swizzle; the dyadic cases bit for bit"""
+    on_sub_views(ctx, monkeypatch, case)
+
+
+@pytest.mark.parametrize("case", R.REFUSED + R.GEOMETRY_REFUSED + R.WINO_REFUSED, ids=lambda c: c.id)
 def test_forced_geometry_refuses_what_it_cannot_run(ctx, monkeypatch, case):
     """an epilogue, a retired id or a geometry the kernel's eligibility rules out is an error, not something ignored: conv_*_eligible
     and the checks of accel_hip.cpp / launch_conv_igemm (conv_ref.RULES restates those of the geometry sweep)"""
