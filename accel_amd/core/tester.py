@@ -211,9 +211,9 @@ class Predictor(object):
         if tag is None or res.get("data") != tag:
             if tag is not None and pre.get("data") == tag:
                 if isinstance(data, NV12Frames):     # its BYTES were prefetched (the same uint8 shadow): colour conversion included
-                    m.commit_nv12("data", *_nv12_layout(data), **data.geometry)
+                    m.commit_nv12("data", *_nv12_layout(data), siting=data.siting, **data.geometry)
                 elif isinstance(data, YUVFrames):    # I420 / P010 / YUY2 bytes, through the same uint8 shadow
-                    m.commit_yuv("data", data.layout["n"], data.layout, data.means, **data.geometry)
+                    m.commit_yuv("data", data.layout["n"], data.layout, data.means, siting=data.siting, **data.geometry)
                 elif isinstance(data, RawFrames):    # its BYTES were prefetched (uint8 shadow): converted on the way into `data`
                     m.commit_u8("data", *_u8_layout(data), **data.geometry)
                 else:
@@ -342,10 +342,10 @@ def _write_image(m, buf, arr):
     if isinstance(arr, NV12Frames):
         lay = arr.layout
         m.write_nv12(buf, arr.nv12, lay["h"], lay["w"], arr.means, pitch=lay["pitch"], uv_offset=lay["uv_offset"], frame_bytes=lay["frame_bytes"],
-                     colour=lay["colour"], **arr.geometry)
+                     colour=lay["colour"], siting=arr.siting, **arr.geometry)
     elif isinstance(arr, YUVFrames):       # (NV12Frames and YUVFrames are siblings under RawFrames: both are asked before it)
         lay = arr.layout
-        m.write_yuv(buf, arr.yuv, lay["format"], lay["h"], lay["w"], arr.means, colour=lay["colour"],
+        m.write_yuv(buf, arr.yuv, lay["format"], lay["h"], lay["w"], arr.means, colour=lay["colour"], siting=arr.siting,
                     **{k: lay[k] for k in ("pitch", "pitch_c", "u_offset", "v_offset", "frame_bytes")}, **arr.geometry)
     elif isinstance(arr, RawFrames):
         m.write_u8(buf, arr.frames, arr.means, **arr.geometry)

@@ -564,6 +564,134 @@ extern "C" int accel_model_commit_yuv(accel_model* m, const char* buf, int n, co
     });
 }
 
+// ---- the same frames, and NV12 as format 3, with interpolated chroma siting (frames_sited.hip) -------------------------------------------
+enum { YUV_NV12 = 3 };
+
+// one past the last byte of a frame, format 3 included: its last chroma row ends after w bytes
+static size_t sited_extent(const accel_yuv_layout& y)
+{
+    if (y.format == YUV_NV12) return y.u_offset + ((size_t)y.h / 2 - 1) * y.pitch + (size_t)y.w;
+    return yuv_extent(y);
+}
+
+static size_t sited_bytes(int n, const accel_yuv_layout& y)
+{
+    return (size_t)(n - 1) * y.frame_bytes + sited_extent(y);
+}
+
+// Layout and siting, checked before anything is enqueued: what yuv_layout_args asks of formats 0 .. 2, NV12's fields of format 3, siting 0 .. 3.
+static int yuv_sited_layout_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev)
+{
+    const int lim = 32768;
+    if (!yuv) return fail(ACCEL_ERR_ARG, "%s: yuv is NULL", fn);
+    if (!lay) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
+    if (siting < 0 || siting > 3) return fail(ACCEL_ERR_ARG, "%s: siting = %d, must be 0 (replicate), 1 (left), 2 (centre) or 3 (topleft)", fn, siting);
+    const accel_yuv_layout& y = *lay;
+    if (y.format < 0 || y.format > 3) return fail(ACCEL_ERR_ARG, "%s: format = %d, must be 0 (I420), 1 (P010), 2 (YUY2) or 3 (NV12)", fn, y.format);
+    if (y.format != YUV_NV12) return yuv_layout_args(fn, yuv, n, lay, dev);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (y.colour < 0 || y.colour > 3)
+        return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, y.colour);
+    if (y.h < 2 || y.h > lim || y.h % 2) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be even and in 2 .. %d for NV12", fn, y.h, lim);
+    if (y.w < 2 || y.w > lim || y.w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 2 .. %d for NV12", fn, y.w, lim);
+    if (y.pitch < (size_t)y.w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d NV12 pixels has %d", fn, y.pitch, y.w, y.w);
+    if (y.pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, y.pitch);
+    if (y.pitch_c) return fail(ACCEL_ERR_ARG, "%s: pitch_c = %zu, but NV12 has no such field: it must be 0", fn, y.pitch_c);
+    if (y.v_offset) return fail(ACCEL_ERR_ARG, "%s: v_offset = %zu, but NV12 has no such field: it must be 0", fn, y.v_offset);
+    const size_t luma_end = (size_t)y.h * y.pitch;
+    if (y.u_offset < luma_end || y.u_offset > ((size_t)1 << 60))
+        return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.u_offset, y.h, y.pitch, luma_end);
+    if (y.frame_bytes < sited_extent(y))
+        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the last plane of a frame ends at %zu", fn, y.frame_bytes, sited_extent(y));
+    if (y.frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, y.frame_bytes);
+    return 0;
+}
+
+static int frame_yuv_sited_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev,
+                                const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    if (int rc = yuv_sited_layout_args(fn, yuv, n, lay, siting, dev)) return rc;
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    return frame_resize_args(fn, lay->h, lay->w, out_h, out_w, step, H, W);
+}
+
+extern "C" int accel_frame_yuv_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
+                                     int out_w, double step, int H, int W, float* out, int siting)
+{
+    const char* fn = "accel_frame_yuv_sited";
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_yuv_sited: NULL argument");
+    if (int rc = frame_yuv_sited_args(fn, yuv, n, layout, siting, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ob = (size_t)n * 3 * H * W * 4;
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, sited_bytes(n, *layout)));
+    float* d = static_cast<float*>(t.get(ob));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_frames_yuv_sited(s, n, kernel_layout(*layout), siting, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_yuv_to_bgr_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch,
+                                      int siting, int on_device)
+{
+    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: NULL argument");
+    if (int rc = yuv_sited_layout_args("accel_yuv_to_bgr_sited", yuv, n, layout, siting, on_device ? yuv : nullptr)) return rc;
+    const int h = layout->h, w = layout->w;
+    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: bgr_out is NULL");
+    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
+        return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on_device) {
+        HIP_TRY(launch_yuv_to_bgr_sited(yuv, n, kernel_layout(*layout), siting, bgr_out, out_pitch, ctx->stream));
+        return 0;
+    }
+    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, sited_bytes(n, *layout)));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_yuv_to_bgr_sited: device allocation or upload failed");
+    HIP_TRY(launch_yuv_to_bgr_sited(s, n, kernel_layout(*layout), siting, d, (size_t)3 * w, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int accel_model_write_yuv_sited(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout,
+                                           const double* means_bgr, int out_h, int out_w, double step, int H, int W, int siting, int src_on_device)
+{
+    const char* fn = "accel_model_write_yuv_sited";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_yuv_sited: NULL argument");
+    if (int rc = frame_yuv_sited_args(fn, yuv, n, layout, siting, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    const YuvLayout y = kernel_layout(*layout);
+    return write_frames(fn, m, buf, n, H, W, yuv, sited_bytes(n, *layout), src_on_device, [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_yuv_sited(src, n, y, siting, means_bgr, out_h, out_w, step, H, W, dst, st);
+    });
+}
+
+// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow, as for accel_model_commit_yuv)
+extern "C" int accel_model_commit_yuv_sited(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
+                                            int out_w, double step, int H, int W, int siting)
+{
+    const char* fn = "accel_model_commit_yuv_sited";
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: NULL argument");
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: unknown buffer '%s'", buf);
+    Shadow* sh = prefetched(m->shadows_u8, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: no uint8 frames were prefetched for '%s'", buf);
+    if (int rc = frame_yuv_sited_args(fn, sh->mem.ptr, n, layout, siting, sh->mem.ptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    const size_t need = sited_bytes(n, *layout);
+    if (need > sh->filled)
+        return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: (n - 1) x frame_bytes + the extent of a frame = %zu bytes, %zu were prefetched for '%s'",
+                    need, sh->filled, buf);
+    const YuvLayout y = kernel_layout(*layout);
+    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
+        return launch_frames_yuv_sited(src, n, y, siting, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
+    });
+}
+
 // ---- finished frames: labels at the source size, confusion matrix, colour image (results_u8.hip) ---------------------------------------
 // Geometry shared by the three, checked before anything is enqueued: every message names the argument at fault.
 static int results_args(const char* fn, int n, int H, int W, int out_h, int out_w, int h, int w)

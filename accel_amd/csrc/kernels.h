@@ -170,6 +170,14 @@ const int32_t* yuv10_coefficients(int colour);
 hipError_t launch_frames_yuv(const unsigned char* src, int n, const YuvLayout& y, const double* means_bgr, int out_h, int out_w, double step,
                              int H, int W, float* dst, hipStream_t st);
 hipError_t launch_yuv_to_bgr(const unsigned char* src, int n, const YuvLayout& y, unsigned char* dst, size_t out_pitch, hipStream_t st);
+// The same with interpolated chroma siting (frames_sited.hip): `siting` 1 left, 2 centre, 3 topleft -- Cb and Cr are interpolated to the luma
+// pixel by the integer rule of image.chroma_upsample before the colour rule -- the tensor and the bytes of image.yuv_to_bgr_host(siting = s),
+// bit for bit.  Format 3 is NV12 here: interleaved 8-bit chroma at `u_offset`, rows `pitch` apart (image.nv12_to_bgr_host).  Siting 0 calls the
+// launchers above, and those of NV12 for format 3.
+hipError_t launch_frames_yuv_sited(const unsigned char* src, int n, const YuvLayout& y, int siting, const double* means_bgr, int out_h, int out_w,
+                                   double step, int H, int W, float* dst, hipStream_t st);
+hipError_t launch_yuv_to_bgr_sited(const unsigned char* src, int n, const YuvLayout& y, int siting, unsigned char* dst, size_t out_pitch,
+                                   hipStream_t st);
 // finished frames (results_u8.hip): n label maps of H x W bytes (valid region out_h x out_w, top left) taken to the source size h x w by the
 // integer nearest rule labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)] -- as labels (rows `dst_pitch` apart), as counts added
 // to an ncls x ncls matrix of 64-bit words (rows gt, columns prediction, ids >= ncls ignored; ncls <= 32), or as n x h x w x 3 colours

@@ -22,7 +22,7 @@ import numpy as np
 from . import mx
 from .config.config import config, update_config
 from .core.tester import Predictor, im_segment
-from .utils.image import NV12_COLOURS, YUV_FORMATS, bgr_to_nv12_host, bgr_to_yuv_host, resize, transform
+from .utils.image import CHROMA_SITINGS, NV12_COLOURS, YUV_FORMATS, bgr_to_nv12_host, bgr_to_yuv_host, resize, transform
 from .utils.tictoc import tic, toc
 
 
@@ -65,7 +65,7 @@ def get_symbols(version, cfg):
     return inst, inst.get_key_test_symbol(cfg), inst.get_cur_test_symbol(cfg)
 
 
-def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None, yuv=None, yuv_colour='bt709'):
+def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None, yuv=None, yuv_colour='bt709', siting='replicate'):
     """demo.py:165-190: list of [data, data_key, feat_key] arrays per frame.
 
     One array per frame serves as this frame's `data` and as the next frame's `data_key` (the reference builds two
@@ -77,7 +77,12 @@ def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None, yuv=None,
     nv12=<colour mode> (utils.image.NV12_COLOURS) feeds every frame as NV12 bytes (mx.nd.nv12_frames), as a video decoder would hand it
     out -- bgr_to_nv12_host stands in for the decoder; an eighth of the bytes cross PCIe and the GPU converts the colour as well.
     yuv=<format> (utils.image.YUV_FORMATS) feeds every frame as I420, P010 or YUY2 bytes (mx.nd.yuv_frames) converted with `yuv_colour`, the
-    same way -- bgr_to_yuv_host stands in for the decoder or the capture card."""
+    same way -- bgr_to_yuv_host stands in for the decoder or the capture card.
+    siting=<name> (utils.image.CHROMA_SITINGS), with nv12 or yuv: the stand-in decoder sites its chroma samples that way and the GPU interpolates
+    them back accordingly; replicate: samples made as block means (centre) and replicated, as ever."""
+    if siting not in CHROMA_SITINGS:
+        raise ValueError("siting = %r, must be one of %s" % (siting, ", ".join(sorted(CHROMA_SITINGS))))
+    made = 'centre' if siting == 'replicate' else siting      # how the stand-in decoder sites its samples
     data, prev = [], None
     ctx = mx.cpu_pinned() if pinned else None
     zero_feat = mx.nd.array(np.zeros((1, cfg.network.DFF_FEAT_DIM, 1, 1)))
@@ -86,12 +91,12 @@ def build_batches(frames_bgr, cfg, pinned=False, raw=False, nv12=None, yuv=None,
             h, w = im.shape[:2]
             if h % 2 or w % 2:
                 raise ValueError("--nv12: NV12 frames have an even height and width, this frame is %d x %d (odd-sized)" % (h, w))
-            cur = mx.nd.nv12_frames(bgr_to_nv12_host(im, nv12), h, w, cfg, colour=nv12, ctx=ctx)
+            cur = mx.nd.nv12_frames(bgr_to_nv12_host(im, nv12, siting=made), h, w, cfg, colour=nv12, ctx=ctx, siting=siting)
         elif yuv is not None:
             h, w = im.shape[:2]
             if h % 2 or w % 2:
                 raise ValueError("--yuv: the %s frames made here have an even height and width, this frame is %d x %d (odd-sized)" % (yuv, h, w))
-            cur = mx.nd.yuv_frames(bgr_to_yuv_host(im, yuv, yuv_colour), yuv, h, w, cfg, colour=yuv_colour, ctx=ctx)
+            cur = mx.nd.yuv_frames(bgr_to_yuv_host(im, yuv, yuv_colour, siting=made), yuv, h, w, cfg, colour=yuv_colour, ctx=ctx, siting=siting)
         elif raw:
             cur = mx.nd.raw_frames(im, cfg, ctx=ctx)
         else:
@@ -201,6 +206,10 @@ def main(argv=None):
                          '--raw-frames, excludes --nv12): the frames, of even height and width, are turned into that format on the host and '
                          'the GPU converts the colour with the matrix of --yuv-colour, resizes, mean-subtracts and pads')
     ap.add_argument('--yuv-colour', dest='yuv_colour', default='bt709', choices=sorted(NV12_COLOURS), help='the colour mode of --yuv')
+    ap.add_argument('--chroma-siting', dest='chroma_siting', default='replicate', choices=sorted(CHROMA_SITINGS, key=CHROMA_SITINGS.get),
+                    help='with --nv12 or --yuv: where the chroma samples of the frames lie -- left (H.264 / HEVC), centre (JPEG) or topleft '
+                         '(BT.2020) -- the stand-in decoder sites them so and the GPU interpolates Cb and Cr to every luma pixel; replicate '
+                         '(default): every pixel takes the sample of its 2 x 2 block')
     ap.add_argument('--finish-on-gpu', dest='finish_on_gpu', action='store_true',
                     help='finish every frame on the GPU: the timed loop fetches the labels at the SOURCE frame\'s size (padding and '
                          'resize undone there), the confusion matrix of the mIoU accumulates in HBM and --out writes those labels; '
@@ -229,6 +238,8 @@ def main(argv=None):
         raise ValueError("--interpolate needs --finish-on-gpu")
     if args.nv12 and args.yuv:
         raise ValueError("--nv12 and --yuv are mutually exclusive: the frames are fed in one format")
+    if args.chroma_siting != 'replicate' and not (args.nv12 or args.yuv):
+        raise ValueError("--chroma-siting needs --nv12 or --yuv: only subsampled frames have a chroma siting")
     if args.nv12 or args.yuv:
         args.raw_frames = True
     if args.cfg:
@@ -284,7 +295,7 @@ def main(argv=None):
         arg_params, aux_params = synth.model_params(version, H, W, config)
 
     data = build_batches(frames, config, pinned=not args.pageable, raw=args.raw_frames, nv12=args.nv12, yuv=args.yuv,
-                         yuv_colour=args.yuv_colour)
+                         yuv_colour=args.yuv_colour, siting=args.chroma_siting)
     runner = ClipRunner(version, config, arg_params, aux_params, (H, W))
     for j in range(min(2, len(data))):       # warm up (demo.py:207-220)
         runner.step(j, data[j], interv)[1].asnumpy()

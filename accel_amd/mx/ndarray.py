@@ -136,8 +136,10 @@ class NV12Frames(RawFrames):
     `.nv12` holds the bytes (n x frame_bytes), `.layout` what the C ABI is told about them; `.frames` is the BGR conversion computed on the
     host on first use, for consumers that want the picture (core.results), and `.asnumpy()` the tensor computed from it."""
 
-    def __init__(self, buf, h, w, pixel_means, target_size, max_size, stride=0, colour="bt601", pitch=None, uv_offset=None, frame_bytes=None, ctx=None):
+    def __init__(self, buf, h, w, pixel_means, target_size, max_size, stride=0, colour="bt601", pitch=None, uv_offset=None, frame_bytes=None, ctx=None,
+                 siting="replicate"):
         from ..utils import image
+        siting = image.chroma_siting(siting)
         if isinstance(buf, (list, tuple)):
             if len({np.shape(f) for f in buf}) != 1:
                 raise ValueError("all frames of one NV12 array must have the same number of bytes")
@@ -162,6 +164,7 @@ class NV12Frames(RawFrames):
         DeviceArray.__init__(self, shape=(n, 3, H, W), fetch=self._host_tensor, pinned=pb)
         self.nv12 = nv12
         self.layout = dict(n=n, colour=image.nv12_colour(colour), **lay)
+        self.siting = siting      # how chroma is brought to the luma pixels (utils.image.CHROMA_SITINGS), a number
         self._frames = None
         self.means = tuple(float(v) for v in np.asarray(pixel_means, np.float64).reshape(-1))
         self.resize_args = (target_size, max_size, stride)
@@ -174,7 +177,8 @@ class NV12Frames(RawFrames):
         if self._frames is None:
             from ..utils import image
             lay = self.layout
-            f = image.nv12_to_bgr_host(self.nv12, lay["h"], lay["w"], lay["pitch"], lay["uv_offset"], lay["frame_bytes"], lay["colour"])
+            f = image.nv12_to_bgr_host(self.nv12, lay["h"], lay["w"], lay["pitch"], lay["uv_offset"], lay["frame_bytes"], lay["colour"],
+                                       siting=self.siting)
             f.setflags(write=False)
             self._frames = f
         return self._frames
@@ -183,15 +187,16 @@ class NV12Frames(RawFrames):
         return "<NV12Frames %dx%dx%d for %s>" % (self.layout["n"], self.layout["h"], self.layout["w"], "x".join(map(str, self._shape)))
 
 
-def nv12_frames(buf, h, w, cfg, colour="bt601", pitch=None, uv_offset=None, ctx=None):
+def nv12_frames(buf, h, w, cfg, colour="bt601", pitch=None, uv_offset=None, ctx=None, siting="replicate"):
     """NV12 frames of h x w pixels (uint8 bytes: one flat frame, n x frame_bytes, a flat run of whole frames, or a list of frames) for a
     Predictor: converted with `colour` (utils.image.NV12_COLOURS), resized to cfg.SCALES[0], centred on cfg.network.PIXEL_MEANS and padded
     to cfg.network.IMAGE_STRIDE on the GPU.  pitch: bytes per row (default w); uv_offset: where the chroma plane starts (default
     h * pitch); the bytes from frame to frame are the row length of an n x frame_bytes buffer, else those of one tightly laid-out frame.
+    siting: where the chroma samples lie (utils.image.CHROMA_SITINGS): replicate, or left / centre / topleft for interpolated chroma.
     Always a COPY of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
     target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
     return NV12Frames(buf, h, w, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, colour=colour, pitch=pitch,
-                      uv_offset=uv_offset, ctx=ctx)
+                      uv_offset=uv_offset, ctx=ctx, siting=siting)
 
 
 class YUVFrames(RawFrames):
@@ -202,8 +207,9 @@ class YUVFrames(RawFrames):
     colour); `.frames` is the BGR conversion computed on the host on first use, for consumers that want the picture (core.results), and
     `.asnumpy()` the tensor computed from it."""
 
-    def __init__(self, buf, fmt, h, w, pixel_means, target_size, max_size, stride=0, colour="bt709", ctx=None, **layout):
+    def __init__(self, buf, fmt, h, w, pixel_means, target_size, max_size, stride=0, colour="bt709", ctx=None, siting="replicate", **layout):
         from ..utils import image
+        siting = image.chroma_siting(siting)
         if isinstance(buf, (list, tuple)):
             if len({np.shape(f) for f in buf}) != 1 or len({np.asarray(f).dtype for f in buf}) != 1:
                 raise ValueError("all frames of one YUV array must have the same number of bytes")
@@ -226,6 +232,7 @@ class YUVFrames(RawFrames):
         DeviceArray.__init__(self, shape=(n, 3, H, W), fetch=self._host_tensor, pinned=pb)
         self.yuv = yuv
         self.layout = dict(n=n, colour=image.nv12_colour(colour), **lay)
+        self.siting = siting      # how chroma is brought to the luma pixels (utils.image.CHROMA_SITINGS), a number
         self._frames = None
         self.means = tuple(float(v) for v in np.asarray(pixel_means, np.float64).reshape(-1))
         self.resize_args = (target_size, max_size, stride)
@@ -238,7 +245,8 @@ class YUVFrames(RawFrames):
         if self._frames is None:
             from ..utils import image
             lay = {k: v for k, v in self.layout.items() if k not in ("n", "colour", "format", "h", "w")}
-            f = image.yuv_to_bgr_host(self.yuv, self.layout["format"], self.layout["h"], self.layout["w"], colour=self.layout["colour"], **lay)
+            f = image.yuv_to_bgr_host(self.yuv, self.layout["format"], self.layout["h"], self.layout["w"], colour=self.layout["colour"],
+                                      siting=self.siting, **lay)
             f.setflags(write=False)
             self._frames = f
         return self._frames
@@ -249,15 +257,17 @@ class YUVFrames(RawFrames):
         return "<YUVFrames %s %dx%dx%d for %s>" % (name, self.layout["n"], self.layout["h"], self.layout["w"], "x".join(map(str, self._shape)))
 
 
-def yuv_frames(buf, fmt, h, w, cfg, colour="bt709", pitch=None, pitch_c=None, u_offset=None, v_offset=None, frame_bytes=None, ctx=None):
+def yuv_frames(buf, fmt, h, w, cfg, colour="bt709", pitch=None, pitch_c=None, u_offset=None, v_offset=None, frame_bytes=None, ctx=None,
+               siting="replicate"):
     """I420, P010 or YUY2 frames (`fmt`: utils.image.YUV_FORMATS) of h x w pixels for a Predictor -- uint8 bytes (uint16 words too for P010): one
     flat frame, n x frame_bytes, a flat run of frames, or a list of frames -- converted with `colour` (utils.image.NV12_COLOURS), resized to
     cfg.SCALES[0], centred on cfg.network.PIXEL_MEANS and padded to cfg.network.IMAGE_STRIDE on the GPU.  The layout keywords are those of
     utils.image.yuv_layout (tightly packed where nothing is given; the bytes from frame to frame default to the row length of an
-    n x frame_bytes buffer).  Always a COPY of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
+    n x frame_bytes buffer).  siting: where the chroma samples lie (utils.image.CHROMA_SITINGS): replicate, or left / centre / topleft for
+    interpolated chroma.  Always a COPY of the bytes; with ctx=mx.cpu_pinned() in page-locked memory."""
     target_size, max_size = cfg.SCALES[0][0], cfg.SCALES[0][1]
     return YUVFrames(buf, fmt, h, w, cfg.network.PIXEL_MEANS, target_size, max_size, cfg.network.IMAGE_STRIDE, colour=colour, ctx=ctx, pitch=pitch,
-                     pitch_c=pitch_c, u_offset=u_offset, v_offset=v_offset, frame_bytes=frame_bytes)
+                     pitch_c=pitch_c, u_offset=u_offset, v_offset=v_offset, frame_bytes=frame_bytes, siting=siting)
 
 
 def zeros(shape, ctx=None, dtype=np.float32):

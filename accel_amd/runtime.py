@@ -93,6 +93,10 @@ def _declare(lib):
         "accel_yuv_to_bgr": [vp, vp, i, c.POINTER(YUVLayout), vp, sz, i],
         "accel_model_write_yuv": [vp, c.c_char_p, vp, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, i],
         "accel_model_commit_yuv": [vp, c.c_char_p, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i],
+        "accel_frame_yuv_sited": [vp, vp, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, vp, i],
+        "accel_yuv_to_bgr_sited": [vp, vp, i, c.POINTER(YUVLayout), vp, sz, i, i],
+        "accel_model_write_yuv_sited": [vp, c.c_char_p, vp, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, i, i],
+        "accel_model_commit_yuv_sited": [vp, c.c_char_p, i, c.POINTER(YUVLayout), vp, i, i, c.c_double, i, i, i],
         "accel_labels_to_source": [vp, vp, i, i, i, i, i, i, i, vp, sz],
         "accel_labels_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, vp],
         "accel_labels_colour": [vp, vp, i, i, i, i, i, i, i, vp, i, vp, sz, i, vp, sz],
@@ -239,6 +243,18 @@ def _yuv_frames(buf, fmt, h, w, colour=0, **layout):
     lay = image.yuv_layout(fmt, h, w, **layout)
     a, n = image.yuv_bytes(buf, lay)
     return a, n, yuv_struct(lay, colour)
+
+
+def _siting(siting):
+    """the number 0 .. 3 of a chroma siting (utils.image.chroma_siting)"""
+    from .utils import image
+    return image.chroma_siting(siting)
+
+
+def nv12_struct(n, h, w, pitch, uv_offset, frame_bytes, colour):
+    """NV12's flat layout as the YUVLayout of format 3 the _sited entry points take (`n` is dropped: the arguments are the tuple of
+    _nv12_frames)"""
+    return YUVLayout(3, int(colour), int(h), int(w), int(pitch), 0, int(uv_offset), 0, int(frame_bytes))
 
 
 def yuv10_coefficients(colour):
@@ -414,49 +430,74 @@ class Context(object):
                                    int(H), int(W), _fp(out)))
         return out
 
-    def frame_nv12(self, buf, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+    def frame_nv12(self, buf, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0, siting=0):
         """accel_frame_nv12: NV12 bytes (uint8, flat or n x frame_bytes; see utils.image.nv12_layout) -> the n x 3 x H x W fp32 tensor
-        transform(resize(nv12_to_bgr_host(..))) gives on the host"""
+        transform(resize(nv12_to_bgr_host(..))) gives on the host.  `siting` (utils.image.chroma_siting) other than replicate:
+        accel_frame_yuv_sited with NV12 as format 3"""
         a, lay = _nv12_frames(buf, h, w, pitch, uv_offset, frame_bytes, colour)
         out = np.empty((lay[0], 3, int(H), int(W)), np.float32)
+        if _siting(siting):
+            check(lib().accel_frame_yuv_sited(self.handle, _fp(a), lay[0], ctypes.byref(nv12_struct(*lay)), _means3(means_bgr), int(out_h), int(out_w),
+                                              float(step), int(H), int(W), _fp(out), _siting(siting)))
+            return out
         check(lib().accel_frame_nv12(self.handle, _fp(a), *lay, _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W), _fp(out)))
         return out
 
-    def nv12_to_bgr(self, buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0, out=None):
+    def nv12_to_bgr(self, buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0, out=None, siting=0):
         """accel_nv12_to_bgr: NV12 bytes -> n x h x w x 3 uint8 BGR (utils.image.nv12_to_bgr_host, on the GPU); `out`: n x h x pitch
-        bytes to write the rows into instead"""
+        bytes to write the rows into instead.  `siting` other than replicate: accel_yuv_to_bgr_sited with NV12 as format 3"""
         a, lay = _nv12_frames(buf, h, w, pitch, uv_offset, frame_bytes, colour)
         out, out_pitch = _result_rows(out, lay[0], lay[1], lay[2], 3)
+        if _siting(siting):
+            check(lib().accel_yuv_to_bgr_sited(self.handle, _fp(a), lay[0], ctypes.byref(nv12_struct(*lay)), _fp(out), out_pitch, _siting(siting), 0))
+            return out
         check(lib().accel_nv12_to_bgr(self.handle, _fp(a), *lay, _fp(out), out_pitch, 0))
         return out
 
-    def nv12_to_bgr_device(self, src_ptr, dst_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, out_pitch):
+    def nv12_to_bgr_device(self, src_ptr, dst_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, out_pitch, siting=0):
         """the same from HBM into HBM (a decoder's output for a viewer, or for the blend of a colour image): only enqueued on the
         context's stream; the caller keeps the source unchanged until the kernel has run"""
+        if _siting(siting):
+            lay = nv12_struct(n, h, w, pitch, uv_offset, frame_bytes, colour)
+            check(lib().accel_yuv_to_bgr_sited(self.handle, ctypes.c_void_p(src_ptr), int(n), ctypes.byref(lay), ctypes.c_void_p(dst_ptr),
+                                               int(out_pitch), _siting(siting), 1))
+            return
         check(lib().accel_nv12_to_bgr(self.handle, ctypes.c_void_p(src_ptr), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
                                       int(colour), ctypes.c_void_p(dst_ptr), int(out_pitch), 1))
 
-    def frame_yuv(self, buf, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, **layout):
+    def frame_yuv(self, buf, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, siting=0, **layout):
         """accel_frame_yuv: I420 / P010 / YUY2 bytes (see utils.image.yuv_layout for the layout keywords, yuv_bytes for the buffer) -> the
-        n x 3 x H x W fp32 tensor transform(resize(yuv_to_bgr_host(..))) gives on the host"""
+        n x 3 x H x W fp32 tensor transform(resize(yuv_to_bgr_host(..))) gives on the host.  `siting` (utils.image.chroma_siting) other
+        than replicate: accel_frame_yuv_sited"""
         a, n, lay = _yuv_frames(buf, fmt, h, w, colour, **layout)
         out = np.empty((n, 3, int(H), int(W)), np.float32)
+        if _siting(siting):
+            check(lib().accel_frame_yuv_sited(self.handle, _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w), float(step),
+                                              int(H), int(W), _fp(out), _siting(siting)))
+            return out
         check(lib().accel_frame_yuv(self.handle, _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W),
                                     _fp(out)))
         return out
 
-    def yuv_to_bgr(self, buf, fmt, h, w, colour=0, out=None, **layout):
+    def yuv_to_bgr(self, buf, fmt, h, w, colour=0, out=None, siting=0, **layout):
         """accel_yuv_to_bgr: I420 / P010 / YUY2 bytes -> n x h x w x 3 uint8 BGR (utils.image.yuv_to_bgr_host, on the GPU); `out`: n x h x pitch
-        bytes to write the rows into instead"""
+        bytes to write the rows into instead.  `siting` other than replicate: accel_yuv_to_bgr_sited"""
         a, n, lay = _yuv_frames(buf, fmt, h, w, colour, **layout)
         out, out_pitch = _result_rows(out, n, lay.h, lay.w, 3)
+        if _siting(siting):
+            check(lib().accel_yuv_to_bgr_sited(self.handle, _fp(a), n, ctypes.byref(lay), _fp(out), out_pitch, _siting(siting), 0))
+            return out
         check(lib().accel_yuv_to_bgr(self.handle, _fp(a), n, ctypes.byref(lay), _fp(out), out_pitch, 0))
         return out
 
-    def yuv_to_bgr_device(self, src_ptr, dst_ptr, n, layout, out_pitch, colour=None):
+    def yuv_to_bgr_device(self, src_ptr, dst_ptr, n, layout, out_pitch, colour=None, siting=0):
         """the same from HBM into HBM (`layout`: a utils.image.yuv_layout dict or a YUVLayout): only enqueued on the context's stream; the caller
         keeps the source unchanged until the kernel has run"""
         lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
+        if _siting(siting):
+            check(lib().accel_yuv_to_bgr_sited(self.handle, ctypes.c_void_p(src_ptr), int(n), ctypes.byref(lay), ctypes.c_void_p(dst_ptr),
+                                               int(out_pitch), _siting(siting), 1))
+            return
         check(lib().accel_yuv_to_bgr(self.handle, ctypes.c_void_p(src_ptr), int(n), ctypes.byref(lay), ctypes.c_void_p(dst_ptr), int(out_pitch), 1))
 
     def labels_to_source(self, labels, out_h, out_w, h, w, out=None):
@@ -778,47 +819,75 @@ class Model(object):
         check(lib().accel_model_commit_u8(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), _means3(means_bgr),
                                           int(out_h), int(out_w), float(step), int(H), int(W)))
 
-    def write_nv12(self, buf, nv12, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
-        """accel_model_write_nv12: host NV12 bytes (see Context.frame_nv12) converted on the GPU into the image input `buf`"""
+    def write_nv12(self, buf, nv12, h, w, means_bgr, out_h, out_w, step, H, W, pitch=None, uv_offset=None, frame_bytes=None, colour=0, siting=0):
+        """accel_model_write_nv12: host NV12 bytes (see Context.frame_nv12) converted on the GPU into the image input `buf`.  `siting` other
+        than replicate: accel_model_write_yuv_sited with NV12 as format 3"""
         a, lay = _nv12_frames(nv12, h, w, pitch, uv_offset, frame_bytes, colour)
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            check(lib().accel_model_write_yuv_sited(self.handle, buf.encode(), _fp(a), lay[0], ctypes.byref(nv12_struct(*lay)), _means3(means_bgr),
+                                                    int(out_h), int(out_w), float(step), int(H), int(W), _siting(siting), 0))
+            return
         check(lib().accel_model_write_nv12(self.handle, buf.encode(), _fp(a), *lay, _means3(means_bgr), int(out_h), int(out_w), float(step),
                                            int(H), int(W), 0))
 
-    def write_nv12_device(self, buf, dev_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W):
+    def write_nv12_device(self, buf, dev_ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, siting=0):
         """the same with the bytes already in HBM (a decoder's output, a torch uint8 tensor's data_ptr()): read in place; the
         caller keeps them unchanged until the kernel has run"""
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            lay = nv12_struct(n, h, w, pitch, uv_offset, frame_bytes, colour)
+            check(lib().accel_model_write_yuv_sited(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), ctypes.byref(lay), _means3(means_bgr),
+                                                    int(out_h), int(out_w), float(step), int(H), int(W), _siting(siting), 1))
+            return
         check(lib().accel_model_write_nv12(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), int(h), int(w), int(pitch), int(uv_offset),
                                            int(frame_bytes), int(colour), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W), 1))
 
-    def commit_nv12(self, buf, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W):
+    def commit_nv12(self, buf, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, siting=0):
         """accel_model_commit_nv12: the compute stream waits for prefetch_u8 (NV12 bytes go through the uint8 shadow), then the kernel
         converts the shadow into `buf`"""
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            lay = nv12_struct(n, h, w, pitch, uv_offset, frame_bytes, colour)
+            check(lib().accel_model_commit_yuv_sited(self.handle, buf.encode(), int(n), ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
+                                                     float(step), int(H), int(W), _siting(siting)))
+            return
         check(lib().accel_model_commit_nv12(self.handle, buf.encode(), int(n), int(h), int(w), int(pitch), int(uv_offset), int(frame_bytes),
                                             int(colour), _means3(means_bgr), int(out_h), int(out_w), float(step), int(H), int(W)))
 
-    def write_yuv(self, buf, yuv, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, **layout):
-        """accel_model_write_yuv: host I420 / P010 / YUY2 bytes (see Context.frame_yuv) converted on the GPU into the image input `buf`"""
+    def write_yuv(self, buf, yuv, fmt, h, w, means_bgr, out_h, out_w, step, H, W, colour=0, siting=0, **layout):
+        """accel_model_write_yuv: host I420 / P010 / YUY2 bytes (see Context.frame_yuv) converted on the GPU into the image input `buf`.
+        `siting` other than replicate: accel_model_write_yuv_sited"""
         a, n, lay = _yuv_frames(yuv, fmt, h, w, colour, **layout)
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            check(lib().accel_model_write_yuv_sited(self.handle, buf.encode(), _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h),
+                                                    int(out_w), float(step), int(H), int(W), _siting(siting), 0))
+            return
         check(lib().accel_model_write_yuv(self.handle, buf.encode(), _fp(a), n, ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
                                           float(step), int(H), int(W), 0))
 
-    def write_yuv_device(self, buf, dev_ptr, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None):
+    def write_yuv_device(self, buf, dev_ptr, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None, siting=0):
         """the same with the bytes already in HBM (`layout`: a utils.image.yuv_layout dict or a YUVLayout): read in place; the caller keeps
         them unchanged until the kernel has run"""
         lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            check(lib().accel_model_write_yuv_sited(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), ctypes.byref(lay), _means3(means_bgr),
+                                                    int(out_h), int(out_w), float(step), int(H), int(W), _siting(siting), 1))
+            return
         check(lib().accel_model_write_yuv(self.handle, buf.encode(), ctypes.c_void_p(dev_ptr), int(n), ctypes.byref(lay), _means3(means_bgr),
                                           int(out_h), int(out_w), float(step), int(H), int(W), 1))
 
-    def commit_yuv(self, buf, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None):
+    def commit_yuv(self, buf, n, layout, means_bgr, out_h, out_w, step, H, W, colour=None, siting=0):
         """accel_model_commit_yuv: the compute stream waits for prefetch_u8 (the bytes go through the uint8 shadow), then the kernel converts
         the shadow into `buf`"""
         lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, colour)
         self.__dict__.get("_resident", {}).pop(buf, None)
+        if _siting(siting):
+            check(lib().accel_model_commit_yuv_sited(self.handle, buf.encode(), int(n), ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
+                                                     float(step), int(H), int(W), _siting(siting)))
+            return
         check(lib().accel_model_commit_yuv(self.handle, buf.encode(), int(n), ctypes.byref(lay), _means3(means_bgr), int(out_h), int(out_w),
                                            float(step), int(H), int(W)))
 

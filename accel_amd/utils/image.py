@@ -316,6 +316,76 @@ def nv12_bytes(buf, layout):
     return a.reshape(-1, fb)
 
 
+# ---- chroma siting ------------------------------------------------------------------------------------------------------------------------------
+# Where the chroma samples of a subsampled frame lie against the luma grid (H.273 chroma_sample_loc_type 0, 1, 2), and the rule that brings
+# them back to every luma pixel.  `replicate` is the nearest-neighbour rule of the routes above: pixel (x, y) takes sample (x >> 1, y >> 1).
+# The others interpolate in integers, per axis with two neighbouring samples and weights that sum to 4 (k = coordinate >> 1):
+#   co-sited (sample k lies on luma 2k)         even coordinate: (k: 4)            odd: (k: 2, k+1: 2)
+#   centred  (sample k lies on luma 2k + 0.5)   even coordinate: (k-1: 1, k: 3)    odd: (k: 3, k+1: 1)
+# indices clamped to the plane, and C = (sum_rows sum_cols wy wx c[row][col] + 8) >> 4: one rounding, none between the axes.  YUY2 has no
+# vertical step (weight 4 on the pixel's own row).  Interlaced siting is not offered.
+#                 horizontal   vertical
+#   1 left        co-sited     centred      H.264 / HEVC default (type 0)
+#   2 centre      centred      centred      JPEG, MPEG-1 (type 1)
+#   3 topleft     co-sited     co-sited     BT.2020 / P010 (type 2)
+CHROMA_SITINGS = {"replicate": 0, "left": 1, "centre": 2, "topleft": 3}
+_SITING_MODES = {1: (0, 1), 2: (1, 1), 3: (0, 0)}      # siting -> (horizontal, vertical): 0 co-sited, 1 centred
+
+
+def chroma_siting(siting):
+    """the number 0 .. 3 of a chroma siting given by name (CHROMA_SITINGS) or by number"""
+    if isinstance(siting, str):
+        if siting not in CHROMA_SITINGS:
+            raise ValueError("siting = %r, must be one of %s" % (siting, ", ".join(sorted(CHROMA_SITINGS))))
+        return CHROMA_SITINGS[siting]
+    if isinstance(siting, (int, np.integer)) and not isinstance(siting, bool) and 0 <= int(siting) <= 3:
+        return int(siting)
+    raise ValueError("siting = %r, must be in 0 .. 3 or one of %s" % (siting, ", ".join(sorted(CHROMA_SITINGS))))
+
+
+def _siting_taps(size, count, mode):
+    """The two taps of every luma coordinate 0 .. size - 1 on an axis with `count` chroma samples: (i0, w0, i1, w1), int64 arrays, indices
+    clamped to [0, count - 1], w0 + w1 == 4.  mode 0 co-sited, 1 centred, None: no step on this axis (sample = coordinate, weight 4)."""
+    x = np.arange(size, dtype=np.int64)
+    if mode is None:
+        return x, np.full(size, 4, np.int64), x, np.zeros(size, np.int64)
+    k, odd = x >> 1, (x & 1).astype(bool)
+    if mode == 0:
+        i0, w0, i1, w1 = k, np.where(odd, 2, 4), np.where(odd, k + 1, k), np.where(odd, 2, 0)
+    else:
+        i0, w0, i1, w1 = np.where(odd, k, k - 1), np.where(odd, 3, 1), np.where(odd, k + 1, k), np.where(odd, 1, 3)
+    return np.clip(i0, 0, count - 1), w0.astype(np.int64), np.clip(i1, 0, count - 1), w1.astype(np.int64)
+
+
+def _sited(fetch, h, w, cw, ch, siting, vertical=True):
+    """the h x w (leading axes kept) int64 array of interpolated chroma: fetch(rows, cols) returns the samples at chroma rows `rows` (h x 1) and
+    columns `cols` (1 x w) -- every sample from wherever the caller keeps it"""
+    hm, vm = _SITING_MODES[siting]
+    x0, wx0, x1, wx1 = (t[None, :] for t in _siting_taps(w, cw, hm))
+    y0, wy0, y1, wy1 = (t[:, None] for t in _siting_taps(h, ch, vm if vertical else None))
+    f = lambda r, c: fetch(r, c).astype(np.int64)
+    total = wy0 * (wx0 * f(y0, x0) + wx1 * f(y0, x1)) + wy1 * (wx0 * f(y1, x0) + wx1 * f(y1, x1))
+    return (total + 8) >> 4
+
+
+def chroma_upsample(plane, h, w, siting, vertical=True):
+    """One chroma plane ([n x] ch x cw, integer samples; cw = w / 2, ch = h / 2, or ch = h where `vertical` is False: YUY2) brought to the
+    h x w luma grid under a siting (the table above).  `replicate`: sample (x >> 1, y >> 1).  Returns int64 in the range of the samples."""
+    s = chroma_siting(siting)
+    p = np.asarray(plane)
+    h, w = int(h), int(w)
+    if p.ndim < 2 or not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("plane must be an integer array [n x] ch x cw, got %s %s" % (p.dtype, p.shape))
+    ch, cw = p.shape[-2:]
+    if h < 1 or w < 2 or w % 2 or cw != w // 2 or ch != (h // 2 if vertical else h) or (vertical and h % 2):
+        raise ValueError("a %d x %d chroma plane does not belong to a %d x %d frame%s" % (ch, cw, h, w, "" if vertical else " without a vertical step"))
+    p = p.astype(np.int64)
+    if s == 0:
+        rows = np.arange(h) >> 1 if vertical else np.arange(h)
+        return np.ascontiguousarray(p[..., rows[:, None], (np.arange(w) >> 1)[None, :]])
+    return _sited(lambda r, c: p[..., r, c], h, w, cw, ch, s, vertical)
+
+
 def yuv_to_bgr(y, cb, cr, colour=0):
     """The integer rule, the specification of csrc/frames_nv12.hip: arrays of Y, Cb, Cr bytes -> (B, G, R) uint8 arrays.  With c = Y - yoff,
     d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts: R = clip((ky c + krv e + 32768) >> 16), G = clip((ky c - kgu d - kgv e +
@@ -328,23 +398,45 @@ def yuv_to_bgr(y, cb, cr, colour=0):
     return clip(c + kbu * d), clip(c - kgu * d - kgv * e), clip(c + krv * e)
 
 
-def nv12_to_bgr_host(buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0):
+def nv12_to_bgr_host(buf, h, w, pitch=None, uv_offset=None, frame_bytes=None, colour=0, siting="replicate"):
     """The specification of accel_nv12_to_bgr, and with resize + transform behind it of accel_frame_nv12: NV12 bytes (uint8, flat or
     n x frame_bytes) -> n x h x w x 3 uint8 BGR.  Pixel (x, y) takes Y at (x, y) and Cb, Cr at (x >> 1, y >> 1) (replicated chroma) through
-    yuv_to_bgr.  Bytes in the gaps -- between rows, between the planes, after a frame -- are not interpreted."""
+    yuv_to_bgr.  Bytes in the gaps -- between rows, between the planes, after a frame -- are not interpreted.  With another `siting`
+    (chroma_siting) Cb and Cr are interpolated by chroma_upsample first: the specification of the _sited entry points with format 3."""
+    siting = chroma_siting(siting)
     lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes)
     h, w, pitch, uv_offset = lay["h"], lay["w"], lay["pitch"], lay["uv_offset"]
     a = nv12_bytes(buf, lay)
     n = a.shape[0]
     luma = a[:, :h * pitch].reshape(n, h, pitch)[:, :, :w]
     uv = a[:, uv_offset:uv_offset + (h // 2) * pitch].reshape(n, h // 2, pitch)[:, :, :w].reshape(n, h // 2, w // 2, 2)
-    up = lambda p: np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)
+    up = (lambda p: np.repeat(np.repeat(p, 2, axis=1), 2, axis=2)) if siting == 0 else (lambda p: chroma_upsample(p, h, w, siting))
     return np.ascontiguousarray(np.stack(yuv_to_bgr(luma, up(uv[..., 0]), up(uv[..., 1]), colour), axis=-1))
 
 
-def bgr_to_nv12_host(frames, colour=0):
+def _subsample(p, siting, vertical=True):
+    """a float64 n x h x w chroma plane at full resolution -> n x h/2 x w/2 (n x h x w/2 without the vertical step) samples sited as `siting`
+    says: centre is the block mean; a co-sited axis takes [1 2 1] / 4 around the even coordinate, the edge replicated"""
+    s = chroma_siting(siting)
+    if s == 0:
+        raise ValueError("frames are fabricated with a siting of their samples: left, centre or topleft, not replicate")
+    hm, vm = _SITING_MODES[s]
+    def axis(q, ax, mode):
+        q = np.moveaxis(q, ax, -1)
+        if mode == 1:
+            q = 0.5 * (q[..., 0::2] + q[..., 1::2])
+        else:
+            e = np.concatenate([q[..., :1], q], axis=-1)
+            q = 0.25 * e[..., 0:-1:2] + 0.5 * q[..., 0::2] + 0.25 * q[..., 1::2]
+        return np.moveaxis(q, -1, ax)
+    p = axis(p, 2, hm)
+    return axis(p, 1, vm) if vertical else p
+
+
+def bgr_to_nv12_host(frames, colour=0, siting="centre"):
     """Tightly packed NV12 bytes (n x h * w * 3 / 2 uint8) of uint8 BGR frames ([n x] h x w x 3, h and w even): the standard's forward matrix
-    in float64, chroma the mean of each 2 x 2 block, rint, clip.  A tool for fabricating inputs (the demo's stand-in for a decoder), NOT the
+    in float64, chroma the mean of each 2 x 2 block, rint, clip.  `siting` left or topleft: chroma sampled on the even column ([1 2 1] / 4, the
+    edge replicated) and, for topleft, on the even row likewise.  A tool for fabricating inputs (the demo's stand-in for a decoder), NOT the
     specification of anything on the GPU, and not an inverse of nv12_to_bgr_host."""
     f = np.asarray(frames)
     if f.ndim == 3:
@@ -358,6 +450,8 @@ def bgr_to_nv12_host(frames, colour=0):
     b, g, r = (f[..., i].astype(np.float64) for i in range(3))
     y = kr * r + kg * g + kb * b
     block = lambda p: p.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4))
+    if chroma_siting(siting) != 2:
+        block = lambda p: _subsample(p, siting)
     cb = 128.0 + block((b - y) / (2.0 * (1.0 - kb))) / s
     cr = 128.0 + block((r - y) / (2.0 * (1.0 - kr))) / s
     q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
@@ -369,7 +463,7 @@ def bgr_to_nv12_host(frames, colour=0):
 
 # ---- I420, P010 and YUY2 frames -----------------------------------------------------------------------------------------------------------------
 # What a software decoder (I420; YV12 is I420 with the chroma planes in the other order), a 10-bit hardware decoder (P010) and a capture card
-# or USB camera (YUY2) hand out.  Frame i starts at byte i * frame_bytes; chroma is replicated, as on the NV12 route.
+# or USB camera (YUY2) hand out.  Frame i starts at byte i * frame_bytes; chroma is replicated, as on the NV12 route, unless a siting is given.
 #   I420   h rows of w luma bytes `pitch` apart from byte 0; the Cb plane at `u_offset` and the Cr plane at `v_offset`, each h/2 rows of w/2 bytes
 #          `pitch_c` apart; pixel (x, y) takes chroma at (x >> 1, y >> 1); h, w even.  The chroma planes start at or after h * pitch and need
 #          not be disjoint from each other (rows interleaved: pitch_c == pitch, v_offset == u_offset + pitch / 2)
@@ -490,33 +584,53 @@ def yuv10_to_bgr(y, cb, cr, colour=0):
     return clip(c + kbu * d), clip(c - kgu * d - kgv * e), clip(c + krv * e)
 
 
-def yuv_to_bgr_host(buf, fmt, h, w, colour=0, **layout):
+def yuv_to_bgr_host(buf, fmt, h, w, colour=0, siting="replicate", **layout):
     """The specification of accel_yuv_to_bgr, and with resize + transform behind it of accel_frame_yuv: I420, P010 or YUY2 bytes (see yuv_bytes;
     the layout keywords are those of yuv_layout) -> n x h x w x 3 uint8 BGR.  Every sample is fetched from its own byte address, so planes may
     interleave or overlap as the layout says; bytes in the gaps are not interpreted.  8-bit samples go through yuv_to_bgr, P010's word >> 6
-    through yuv10_to_bgr."""
+    through yuv10_to_bgr.  With another `siting` (chroma_siting) Cb and Cr are interpolated first -- the rule of chroma_upsample, P010's on the
+    10-bit samples, YUY2's without the vertical step: the specification of the _sited entry points."""
+    siting = chroma_siting(siting)
     lay = yuv_layout(fmt, h, w, **layout)
     a, n = yuv_bytes(buf, lay)
     f, h, w, pitch = lay["format"], lay["h"], lay["w"], lay["pitch"]
     base = (np.arange(n, dtype=np.int64) * lay["frame_bytes"])[:, None, None]
     ys, xs = np.arange(h, dtype=np.int64)[None, :, None], np.arange(w, dtype=np.int64)[None, None, :]
-    if f == 0:
+    word = lambda i: (a[i].astype(np.int32) | a[i + 1].astype(np.int32) << 8) >> 6
+    if siting:
+        # the address of chroma sample (row, col) of every frame: n x rows x cols for index arrays rows (h x 1) and cols (1 x w)
+        cw, ch, vertical = w // 2, (h if f == 2 else h // 2), f != 2
+        if f == 0:
+            at = lambda off: (lambda r, c: a[base + off + r[None] * lay["pitch_c"] + c[None]])
+            cb, cr = at(lay["u_offset"]), at(lay["v_offset"])
+        elif f == 2:
+            at = lambda off: (lambda r, c: a[base + r[None] * pitch + 4 * c[None] + off])
+            cb, cr = at(1), at(3)
+        else:
+            at = lambda off: (lambda r, c: word(base + lay["u_offset"] + r[None] * pitch + 4 * c[None] + off))
+            cb, cr = at(0), at(2)
+        cb, cr = (_sited(g, h, w, cw, ch, siting, vertical) for g in (cb, cr))
+        if f == 1:
+            bgr = yuv10_to_bgr(word(base + ys * pitch + 2 * xs), cb, cr, colour)
+        else:
+            bgr = yuv_to_bgr(a[base + ys * pitch + (xs if f == 0 else 2 * xs)], cb, cr, colour)
+    elif f == 0:
         c = base + (ys >> 1) * lay["pitch_c"] + (xs >> 1)
         bgr = yuv_to_bgr(a[base + ys * pitch + xs], a[lay["u_offset"] + c], a[lay["v_offset"] + c], colour)
     elif f == 2:
         quad = base + ys * pitch + 4 * (xs >> 1)
         bgr = yuv_to_bgr(a[base + ys * pitch + 2 * xs], a[quad + 1], a[quad + 3], colour)
     else:
-        word = lambda i: (a[i].astype(np.int32) | a[i + 1].astype(np.int32) << 8) >> 6
         uv = base + lay["u_offset"] + (ys >> 1) * pitch + 4 * (xs >> 1)
         bgr = yuv10_to_bgr(word(base + ys * pitch + 2 * xs), word(uv), word(uv + 2), colour)
     return np.ascontiguousarray(np.stack(bgr, axis=-1))
 
 
-def bgr_to_yuv_host(frames, fmt, colour=0):
+def bgr_to_yuv_host(frames, fmt, colour=0, siting="centre"):
     """Tightly packed I420, P010 or YUY2 bytes (n x frame_bytes uint8) of uint8 BGR frames ([n x] h x w x 3, h and w even): the standard's forward
     matrix in float64, chroma the mean of each 2 x 2 block (of each pair for YUY2), rint, clip; P010 samples sit in the top ten bits of their
-    words.  A tool for fabricating inputs (the demo's stand-in for a decoder), NOT the specification of anything on the GPU."""
+    words.  `siting` left or topleft: chroma sampled as in bgr_to_nv12_host (for YUY2 both are [1 2 1] / 4 on the even column).  A tool for
+    fabricating inputs (the demo's stand-in for a decoder), NOT the specification of anything on the GPU."""
     fm = yuv_format(fmt)
     f = np.asarray(frames)
     if f.ndim == 3:
@@ -530,6 +644,8 @@ def bgr_to_yuv_host(frames, fmt, colour=0):
     b, g, r = (f[..., i].astype(np.float64) for i in range(3))
     y = kr * r + kg * g + kb * b
     block = (lambda p: p.reshape(n, h, w // 2, 2).mean(axis=3)) if fm == 2 else (lambda p: p.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4)))
+    if chroma_siting(siting) != 2:
+        block = lambda p: _subsample(p, siting, vertical=fm != 2)
     luma = yoff + y / ky
     cb = 128.0 + block((b - y) / (2.0 * (1.0 - kb))) / s
     cr = 128.0 + block((r - y) / (2.0 * (1.0 - kr))) / s

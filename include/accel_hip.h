@@ -214,8 +214,8 @@ int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, 
  *                         between the planes, after a frame -- are never read
  *   colour                0 BT.601 limited range, 1 BT.601 full range, 2 BT.709 limited range, 3 BT.709 full range
  *   means_bgr .. W        as for uint8 frames
- * Pixel (x, y) takes Y at (x, y) and Cb, Cr at (x >> 1, y >> 1) (replicated chroma; interpolated chroma siting is not
- * offered).  With c = Y - yoff, d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts:
+ * Pixel (x, y) takes Y at (x, y) and Cb, Cr at (x >> 1, y >> 1) (replicated chroma; interpolated chroma siting is what
+ * the _sited entry points below offer, NV12 being their format 3).  With c = Y - yoff, d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts:
  *     R = clip((ky*c + krv*e         + 32768) >> 16, 0, 255)
  *     G = clip((ky*c - kgu*d - kgv*e + 32768) >> 16, 0, 255)
  *     B = clip((ky*c + kbu*d         + 32768) >> 16, 0, 255)
@@ -263,7 +263,8 @@ int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w
  * A field the format does not use (pitch_c and v_offset for P010 and YUY2, u_offset for YUY2) must be 0.  P010 holds
  * little-endian 16-bit words whose sample is word >> 6 (the low six bits are never looked at); its pitch, u_offset,
  * frame_bytes and a device source address are multiples of 2.  Bytes in the gaps are never read.
- * Chroma is replicated: I420 and P010 pixel (x, y) takes it at (x >> 1, y >> 1), YUY2 from quad x >> 1 of its own row.
+ * Chroma is replicated: I420 and P010 pixel (x, y) takes it at (x >> 1, y >> 1), YUY2 from quad x >> 1 of its own row
+ * (interpolated siting: the _sited entry points below).
  * The 8-bit formats convert with the rule and the integers of NV12.  P010, with c = Y10 - 4 * yoff, d = Cb10 - 512,
  * e = Cr10 - 512 in int32:
  *     R = clip((ky*c + krv*e         + (1 << 17)) >> 18, 0, 255)
@@ -285,6 +286,38 @@ int accel_model_write_yuv(accel_model* m, const char* buf, const uint8_t* yuv, i
                           int out_h, int out_w, double step, int H, int W, int src_on_device);
 int accel_model_commit_yuv(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr,
                            int out_h, int out_w, double step, int H, int W);
+
+/* ---- interpolated chroma siting ----------------------------------------------------------------------------------------
+ * The routes above replicate chroma: the nearest-neighbour upsampling, which shifts the colour planes by up to half a
+ * chroma sample against the luma plane.  These entry points interpolate Cb and Cr to every luma pixel first, as the
+ * siting of the source says (H.273 chroma_sample_loc_type 0, 1, 2), and hand the result to the colour rule of the format
+ * where the replicated sample enters it above (csrc/frames_sited.hip): the tensor is, bit for bit,
+ * transform(resize(yuv_to_bgr_host(frame, siting = s))) of accel_amd/utils/image.py.  They mirror the four yuv entry
+ * points argument for argument, with a trailing `int siting` (before on_device / src_on_device where those exist):
+ *   siting                0 replicate: the kernels above, bit for bit;  1 left: horizontally co-sited, vertically centred
+ *                         (H.264 / HEVC);  2 centre: centred on both axes (JPEG);  3 topleft: co-sited on both (BT.2020).
+ *                         For YUY2, which has no vertical step, left and topleft coincide.  Interlaced siting is not offered
+ *   format                0 I420, 1 P010, 2 YUY2 as above, and 3 NV12: h rows of w luma bytes `pitch` apart and, at
+ *                         `u_offset` (>= h * pitch), h/2 rows of w/2 (Cb, Cr) byte pairs at the same pitch; pitch_c and
+ *                         v_offset must be 0; h, w even, 2 .. 32768; frame_bytes >= u_offset + (h/2 - 1) * pitch + w
+ * The chroma planes have cw = w/2 columns and ch = h/2 rows (YUY2: ch = h, weight 4 on the pixel's own row).  For luma
+ * pixel (x, y), k = x >> 1 and j = y >> 1, each axis takes two neighbouring samples with weights that sum to 4:
+ *     co-sited (sample k lies on luma 2k)          even coordinate: (k: 4)             odd: (k: 2, k+1: 2)
+ *     centred  (sample k lies on luma 2k + 0.5)    even coordinate: (k-1: 1, k: 3)     odd: (k: 3, k+1: 1)
+ * with indices clamped to [0, cw-1] and [0, ch-1], and for Cb and Cr alike
+ *     C(x, y) = (sum_rows sum_cols wy * wx * c[row][col] + 8) >> 4
+ * -- one rounding, none between the axes; for P010 on the 10-bit word >> 6 samples.  When the frame is resized, each of
+ * the four taps is converted to B, G, R bytes with sited chroma first.
+ * Argument errors (those of the yuv entry points; siting outside 0 .. 3; format outside 0 .. 3; NV12's fields) return
+ * ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument. */
+int accel_frame_yuv_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                          int out_h, int out_w, double step, int H, int W, float* out, int siting);
+int accel_yuv_to_bgr_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch,
+                           int siting, int on_device);
+int accel_model_write_yuv_sited(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout,
+                                const double* means_bgr, int out_h, int out_w, double step, int H, int W, int siting, int src_on_device);
+int accel_model_commit_yuv_sited(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr,
+                                 int out_h, int out_w, double step, int H, int W, int siting);
 
 /* ---- finished frames: labels at the source size, confusion matrix, colour image ------------------------------------
  * The output side of the loop (demo.py:245-266: `.asnumpy()` of the label map, fast_hist, the palette PNG) on the GPU
