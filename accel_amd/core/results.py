@@ -4,7 +4,8 @@ _labels_colour / _hist_add / _hist_read) -- and the logits themselves finished a
 accel_model_confidence), or as labels of their own: `interpolate=True` takes the LOGITS handle, interpolates the scores bilinearly to the
 source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour), and
 `confidence(..., interpolate=True)` takes the confidence from those interpolated scores too, with the labels if asked, in one pass
-(csrc/scores_confidence.hip behind accel_model_confidence_interp).
+(csrc/scores_confidence.hip behind accel_model_confidence_interp).  `overlay` blends the labels over NV12 / I420 / P010 / YUY2 frames and
+hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -85,6 +86,34 @@ def colour(handle, like, palette, frames=None, alpha=256, rgb=True, interpolate=
     if interpolate:
         return m.scores_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
     return m.labels_colour(n, out_h, out_w, h, w, palette, frames=frames, alpha=alpha, rgb=rgb)
+
+
+def overlay(handle, like, palette, alpha=128, interpolate=False):
+    """The labels of `handle` blended over the frames of `like` IN THEIR OWN FORMAT: `like` is the NV12Frames or YUVFrames array the network was
+    fed with, and the result is its bytes -- the shape and dtype of `like.nv12` / `like.yuv`, the same layout, gaps included -- with every sample
+    blended with weight alpha / 256 towards palette[label] (256 x 3 R, G, B, taken to Y, Cb, Cr once with `like`'s colour mode:
+    utils.image.palette_ycbcr; the per-sample rule is utils.image.overlay_yuv_host, on the GPU: csrc/overlay_yuv.hip).  What an encoder or a
+    compositor takes; no BGR picture is made on the way.  The overlay's chroma is the mean of the palette colours over the pixels a chroma
+    sample covers, whatever `like.siting` is: the frame's own samples are blended where they are and are not resited.
+    interpolate=True: `handle` is the LOGITS handle and the labels are those of labels_at_source(handle, like, interpolate=True)."""
+    from ..mx.ndarray import NV12Frames, YUVFrames
+    from ..utils import image
+    if not isinstance(like, (NV12Frames, YUVFrames)):
+        raise ValueError("overlay writes NV12, I420, P010 or YUY2 frames in their own format: `like` must be an NV12Frames or a YUVFrames array, "
+                         "got %s (for a BGR / RGB picture use results.colour)" % type(like).__name__)
+    m = _model(handle, "logits" if interpolate else "labels")
+    lay = like.layout
+    # (the source size from the layout: `like.frames` would convert the frames to BGR on the host, for nothing)
+    n, out_h, out_w, h, w = _geometry(handle, dict(like.geometry, h=lay["h"], w=lay["w"]), scores=bool(interpolate))
+    if isinstance(like, NV12Frames):
+        buf, fmt = like.nv12, 3
+        keys = dict(pitch=lay["pitch"], u_offset=lay["uv_offset"], frame_bytes=lay["frame_bytes"])
+    else:
+        buf, fmt = like.yuv, lay["format"]
+        keys = {k: lay[k] for k in ("pitch", "pitch_c", "u_offset", "v_offset", "frame_bytes")}
+    table = image.palette_ycbcr(palette, lay["colour"], bits=10 if fmt == 1 else 8)
+    run = m.scores_overlay_yuv if interpolate else m.labels_overlay_yuv
+    return run(n, out_h, out_w, buf, fmt, h, w, table, alpha=alpha, **keys)
 
 
 def confidence(handle, like, margin=False, second=False, hist=False, probabilities=None, interpolate=False, labels=False):

@@ -1,6 +1,6 @@
 // libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
-// points behind them -- uint8, NV12, I420, P010 and YUY2 frames in, finished frames, confidence (of stored and of interpolated scores) and interpolated labels out
-// (see include/accel_hip.h).  Nothing here knows about plans.
+// points behind them -- uint8, NV12, I420, P010 and YUY2 frames in, finished frames, confidence (of stored and of interpolated scores), interpolated labels and
+// the overlay in the frame's own format out (see include/accel_hip.h).  Nothing here knows about plans.
 #include <cstring>
 
 #include "accel_objects.h"
@@ -1181,6 +1181,128 @@ extern "C" int accel_model_scores_colour(accel_model* m, int n, int out_h, int o
         const hipError_t e = launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st);
         if (e != hipSuccess) return e;
         return launch_labels_colour(lab, n, h, w, h, w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);   // the scratch at the identity geometry
+    });
+}
+
+// ---- the overlay in the frame's own format (overlay_yuv.hip) ---------------------------------------------------------------------------------
+// What the three entry points share besides the geometry, checked before anything is enqueued: every message names the argument at fault.  The
+// layout by the rules of the frame routes (format 3 = NV12; its `colour` is not looked at: the table holds the colours), `frame_dev` / `dst_dev`:
+// the addresses the kernel will use if the caller's pointers are device memory, else NULL.
+static int overlay_args(const char* fn, int n, const accel_yuv_layout* layout, const uint16_t* palette_ycc, int alpha, const void* frame,
+                        const void* frame_dev, const void* dst, const void* dst_dev, accel_yuv_layout* lay)
+{
+    if (!frame) return fail(ACCEL_ERR_ARG, "%s: frame is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (!palette_ycc) return fail(ACCEL_ERR_ARG, "%s: palette_ycc is NULL", fn);
+    if (!layout) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
+    *lay = *layout;
+    lay->colour = 0;
+    if (int rc = yuv_sited_layout_args(fn, frame, n, lay, 0, nullptr)) return rc;
+    if (lay->format == YUV_P010 && reinterpret_cast<uintptr_t>(frame_dev) % 2)
+        return fail(ACCEL_ERR_ARG, "%s: frame = %p, P010 words are 2-byte aligned: a device address must be even", fn, frame_dev);
+    if (lay->format == YUV_P010 && reinterpret_cast<uintptr_t>(dst_dev) % 2)
+        return fail(ACCEL_ERR_ARG, "%s: dst = %p, P010 words are 2-byte aligned: a device address must be even", fn, dst_dev);
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    const int top = lay->format == YUV_P010 ? 1023 : 255;
+    for (int i = 0; i < 768; ++i)
+        if (palette_ycc[i] > top)
+            return fail(ACCEL_ERR_ARG, "%s: palette_ycc[%d] = %d (label %d, %s), must be in 0 .. %d for this format", fn, i, (int)palette_ycc[i], i / 3,
+                        i % 3 == 0 ? "Y" : i % 3 == 1 ? "Cb" : "Cr", top);
+    if (frame_dev && dst_dev && frame_dev != dst_dev) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(frame_dev), b = reinterpret_cast<uintptr_t>(dst_dev), bytes = (size_t)n * lay->frame_bytes;
+        if (a < b + bytes && b < a + bytes)
+            return fail(ACCEL_ERR_ARG, "%s: dst = %p overlaps frame = %p (n x frame_bytes = %zu bytes each): dst must be the frame itself (in place) "
+                                       "or disjoint from it", fn, dst_dev, frame_dev, (size_t)bytes);
+    }
+    return 0;
+}
+
+extern "C" int accel_labels_overlay_yuv(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, const accel_yuv_layout* layout,
+                                        const uint16_t* palette_ycc, int alpha, const uint8_t* frame, uint8_t* dst)
+{
+    const char* fn = "accel_labels_overlay_yuv";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    accel_yuv_layout lay;
+    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, nullptr, dst, nullptr, &lay)) return rc;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, lay.h, lay.w)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // host in, host out: the destination starts as a copy of the frame, so the bytes that are not samples are the input's
+    DevTemps t;
+    const size_t bytes = sited_bytes(n, lay);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(frame, bytes));
+    unsigned char* d = static_cast<unsigned char*>(t.upload(frame, bytes));
+    if (!l || !s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_overlay_yuv(l, n, H, W, out_h, out_w, kernel_layout(lay), palette_ycc, alpha, s, d, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The frames blended with `lab` (n maps of H x W, valid out_h x out_w) wherever source and destination are.  Device to device: one kernel, and
+// that is all.  A host destination: the frame is brought into the staging buffer (its gaps with it), blended there in place, copied out, and the
+// call waits.  A host frame into device memory goes through the input staging buffer.
+template <class Labels>
+static int overlay_frames(accel_model* m, int n, const accel_yuv_layout& lay, const uint16_t* palette_ycc, int alpha, const uint8_t* frame,
+                          int frame_on_device, uint8_t* dst, int dst_on_device, Labels labels)
+{
+    hipStream_t st = m->ctx->stream;
+    const YuvLayout y = kernel_layout(lay);
+    const size_t bytes = sited_bytes(n, lay);
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (dst_on_device) {
+        const unsigned char* f = frame;
+        if (!frame_on_device) if (int rc = stage_in(m, frame, bytes, &f)) return rc;
+        return labels(f, dst, y, st);
+    }
+    if (int rc = m->stage_out.reserve(m->ctx->device, bytes)) return rc;
+    unsigned char* d = m->stage_out.ptr;
+    if (frame_on_device) HIP_TRY(launch_copy_bytes(frame, d, bytes, st));
+    else HIP_TRY(hipMemcpyAsync(d, frame, bytes, hipMemcpyHostToDevice, st));
+    if (int rc = labels(d, d, y, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_labels_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
+                                              int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device)
+{
+    const char* fn = "accel_model_labels_overlay_yuv";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    accel_yuv_layout lay;
+    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, frame_on_device ? frame : nullptr, dst, dst_on_device ? dst : nullptr, &lay)) return rc;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, lay.h, lay.w)) return rc;
+    return overlay_frames(m, n, lay, palette_ycc, alpha, frame, frame_on_device, dst, dst_on_device,
+                          [&](const unsigned char* f, unsigned char* d, const YuvLayout& y, hipStream_t st) -> int {
+        HIP_TRY(launch_overlay_yuv(labels, n, H, W, out_h, out_w, y, palette_ycc, alpha, f, d, st));
+        return 0;
+    });
+}
+
+extern "C" int accel_model_scores_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
+                                              int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device)
+{
+    const char* fn = "accel_model_scores_overlay_yuv";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    accel_yuv_layout lay;
+    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, frame_on_device ? frame : nullptr, dst, dst_on_device ? dst : nullptr, &lay)) return rc;
+    const int h = lay.h, w = lay.w;
+    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+    unsigned char* lab = m->interp_labels.ptr;
+    return overlay_frames(m, n, lay, palette_ycc, alpha, frame, frame_on_device, dst, dst_on_device,
+                          [&](const unsigned char* f, unsigned char* d, const YuvLayout& y, hipStream_t st) -> int {
+        HIP_TRY(launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
+        HIP_TRY(launch_overlay_yuv(lab, n, h, w, h, w, y, palette_ycc, alpha, f, d, st));       // the scratch at the identity geometry
+        return 0;
     });
 }
 

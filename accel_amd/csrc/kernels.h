@@ -189,6 +189,13 @@ hipError_t launch_labels_hist(const unsigned char* labels, int n, int H, int W, 
                               int ncls, unsigned long long* hist, hipStream_t st);
 hipError_t launch_labels_colour(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, const unsigned char* palette_rgb,
                                 int rgb_order, const unsigned char* frame, size_t frame_pitch, int alpha, unsigned char* dst, size_t dst_pitch, hipStream_t st);
+// the overlay in the frame's own format (overlay_yuv.hip): the same label maps and geometry, h x w = y.h x y.w, blended with weight alpha / 256
+// over n frames laid out as `y` says (formats 0 .. 2 as above, 3 = NV12 as for the sited launchers; y.colour is not looked at) into `dst`, which
+// has the same layout and may be `frame` itself (otherwise disjoint from it).  palette_ycc: 768 host words, (Y, Cb, Cr) per label in the units of
+// the samples (utils/image.py palette_ycbcr).  Integer arithmetic, one rounding per sample: utils/image.py overlay_yuv_host, bit for bit.  Bytes
+// that are not samples are neither read nor written.  labels, frame and dst are device memory; the kernel only reads `labels`
+hipError_t launch_overlay_yuv(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, const YuvLayout& y, const uint16_t* palette_ycc,
+                              int alpha, const unsigned char* frame, unsigned char* dst, hipStream_t st);
 // confidence of finished frames (confidence.hip): n x ncls x H x W fp32 scores (NCHW, the layout of `logits`; ncls in {2, 19, 21}) in the geometry
 // above -> per source pixel conf = min(255, floor(256 * largest softmax probability)) (float64; is_prob: the scores are probabilities, no
 // exponential), margin = l_top1 - l_top2 (fp32), second = the runner-up class, and hist = n x 256 counts of the conf levels per frame (overwritten).

@@ -222,6 +222,10 @@ def main(argv=None):
     ap.add_argument('--interpolate', action='store_true',
                     help='with --finish-on-gpu: the labels at the source size are the argmax of the bilinearly INTERPOLATED scores '
                          '(made on the GPU where the logits are) instead of the nearest label of the finished map; the mIoU counts them')
+    ap.add_argument('--overlay-yuv', dest='overlay_yuv', action='store_true',
+                    help='with --finish-on-gpu and --nv12 or --yuv: the labels blended over the frame IN ITS OWN FORMAT on the GPU (what an '
+                         'encoder or a compositor takes; honours --interpolate); --out writes overlay_<frame>.png, the GPU\'s BGR '
+                         'conversion of those bytes')
     ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
                                                  '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
@@ -238,6 +242,8 @@ def main(argv=None):
         raise ValueError("--interpolate needs --finish-on-gpu")
     if args.nv12 and args.yuv:
         raise ValueError("--nv12 and --yuv are mutually exclusive: the frames are fed in one format")
+    if args.overlay_yuv and not (args.finish_on_gpu and (args.nv12 or args.yuv)):
+        raise ValueError("--overlay-yuv needs --finish-on-gpu and one of --nv12 / --yuv: the overlay is written in the frame's own format")
     if args.chroma_siting != 'replicate' and not (args.nv12 or args.yuv):
         raise ValueError("--chroma-siting needs --nv12 or --yuv: only subsampled frames have a chroma siting")
     if args.nv12 or args.yuv:
@@ -335,6 +341,20 @@ def main(argv=None):
             seg = Image.fromarray(pred)
             seg.putpalette(getpallete(256))
             seg.save(os.path.join(args.out, 'seg_' + os.path.basename(names[idx])))
+        if args.overlay_yuv:      # after the clock: the frame's own bytes with the labels blended in, shown through the GPU's own conversion
+            from .dataset.cityscape import getpallete
+            like = arrays[0]
+            over = results.overlay(lg if args.interpolate else lab, like, getpallete(256), interpolate=args.interpolate)
+            if args.out:
+                from PIL import Image
+                ctx, lay = lab.device_ref[0].ctx, like.layout
+                if args.nv12:
+                    bgr = ctx.nv12_to_bgr(over, lay['h'], lay['w'], lay['pitch'], lay['uv_offset'], lay['frame_bytes'], lay['colour'], siting=like.siting)
+                else:
+                    keys = {k: lay[k] for k in ('pitch', 'pitch_c', 'u_offset', 'v_offset', 'frame_bytes')}
+                    bgr = ctx.yuv_to_bgr(over, lay['format'], lay['h'], lay['w'], colour=lay['colour'], siting=like.siting, **keys)
+                os.makedirs(args.out, exist_ok=True)
+                Image.fromarray(np.ascontiguousarray(bgr[0][:, :, ::-1])).save(os.path.join(args.out, 'overlay_' + os.path.basename(names[idx])))
         lf = labels.get(label_key(names[idx]))
         if lf is not None:
             from PIL import Image

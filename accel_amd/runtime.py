@@ -112,6 +112,9 @@ def _declare(lib):
         "accel_model_scores_labels": [vp, i, i, i, i, i, vp, sz, i],
         "accel_model_scores_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
         "accel_model_scores_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
+        "accel_labels_overlay_yuv": [vp, vp, i, i, i, i, i, c.POINTER(YUVLayout), vp, i, vp, vp],
+        "accel_model_labels_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
+        "accel_model_scores_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
         "accel_comm_available": [],
         "accel_comm_unique_id": [vp],
         "accel_comm_create": [vp, i, i, vp, c.POINTER(vp)],
@@ -287,6 +290,28 @@ def _palette(palette):
     if p.size != 768:
         raise ValueError("the palette must hold 256 x 3 bytes (R, G, B), got %d" % p.size)
     return p
+
+
+def _overlay_frames(buf, fmt, h, w, **layout):
+    """frames an overlay is written over, as the C ABI takes them: (contiguous flat uint8 array, n, YUVLayout, shape of the result); `fmt` and the
+    keywords are those of utils.image.overlay_layout (formats 0 .. 2 and "nv12" / 3)"""
+    from .utils import image
+    lay = image.overlay_layout(fmt, h, w, **layout)
+    src = np.asarray(buf)
+    if lay["format"] == 3:
+        a = np.ascontiguousarray(image.nv12_bytes(src, lay)).reshape(-1)
+        n = a.size // lay["frame_bytes"]
+    else:
+        a, n = image.yuv_bytes(src, lay)
+    return a, n, yuv_struct(lay, 0), (src.shape if src.dtype == np.uint8 else a.shape)
+
+
+def _table_ycc(table, fmt_number):
+    t = np.ascontiguousarray(np.asarray(table).reshape(-1))
+    top = 1023 if fmt_number == 1 else 255
+    if t.size != 768 or not np.issubdtype(t.dtype, np.integer) or t.min() < 0 or t.max() > 65535:
+        raise ValueError("the table must hold 256 x 3 integers (Y, Cb, Cr) in 0 .. %d (utils.image.palette_ycbcr)" % top)
+    return np.ascontiguousarray(t.astype(np.uint16))
 
 
 def _result_rows(out, n, h, w, channels):
@@ -532,6 +557,20 @@ class Context(object):
         check(lib().accel_labels_colour(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)),
                                         int(bool(rgb)), None if f is None else _fp(f), fp, int(alpha), _fp(out), pitch))
         return out
+
+    def labels_overlay_yuv(self, labels, out_h, out_w, buf, fmt, h, w, table, alpha=128, **layout):
+        """accel_labels_overlay_yuv: n x H x W label maps whose valid region is out_h x out_w, blended over the frames in `buf` (I420 / P010 / YUY2
+        / "nv12"; the layout keywords of utils.image.overlay_layout) with the colours `table` (256 x 3 Y, Cb, Cr: utils.image.palette_ycbcr) ->
+        the bytes of the same frames in the same layout, uint8 in the shape of `buf` (utils.image.overlay_yuv_host of the labels at the source
+        size, on the GPU)"""
+        a, n, H, W, _ = _u8_maps(labels)
+        f, fn, lay, shape = _overlay_frames(buf, fmt, h, w, **layout)
+        if fn != n:
+            raise ValueError("%d label maps but %d frames" % (n, fn))
+        out = f.copy()      # the library fills n frames up to the last sample of the last one; what a buffer holds behind that is the input's too
+        check(lib().accel_labels_overlay_yuv(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), ctypes.byref(lay), _fp(_table_ycc(table, lay.format)),
+                                             int(alpha), _fp(f), _fp(out)))
+        return out.reshape(shape)
 
     def scores_confidence(self, scores, out_h, out_w, h, w, is_prob=False, conf=True, margin=True, second=True, hist=True):
         """accel_scores_confidence: n x ncls x H x W scores whose valid region is out_h x out_w -> (conf, margin, second, hist) at the
@@ -998,6 +1037,38 @@ class Model(object):
         check(lib().accel_model_scores_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
                                               None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
         return out
+
+    # ---- the overlay in the frame's own format: they only READ `labels` / `logits` -------------------------------------------------
+    def _overlay_yuv(self, fn, n, out_h, out_w, buf, fmt, h, w, table, alpha, layout):
+        f, fn_, lay, shape = _overlay_frames(buf, fmt, h, w, **layout)
+        if fn_ != int(n):
+            raise ValueError("%d frames for a result of %d" % (fn_, n))
+        out = f.copy()      # the library fills n frames up to the last sample of the last one; what a buffer holds behind that is the input's too
+        check(fn(self.handle, int(n), int(out_h), int(out_w), ctypes.byref(lay), _fp(_table_ycc(table, lay.format)), int(alpha), _fp(f), 0, _fp(out), 0))
+        return out.reshape(shape)
+
+    def _overlay_yuv_device(self, fn, src_ptr, dst_ptr, n, out_h, out_w, layout, table, alpha):
+        lay = layout if isinstance(layout, YUVLayout) else yuv_struct(layout, 0)
+        check(fn(self.handle, int(n), int(out_h), int(out_w), ctypes.byref(lay), _fp(_table_ycc(table, lay.format)), int(alpha),
+                 ctypes.c_void_p(src_ptr) if src_ptr else None, 1, ctypes.c_void_p(dst_ptr) if dst_ptr else None, 1))
+
+    def labels_overlay_yuv(self, n, out_h, out_w, buf, fmt, h, w, table, alpha=128, **layout):
+        """accel_model_labels_overlay_yuv: the first n maps of `labels` blended over the host frames in `buf` (see Context.labels_overlay_yuv)
+        -> the bytes of the same frames in the same layout, uint8 in the shape of `buf`"""
+        return self._overlay_yuv(lib().accel_model_labels_overlay_yuv, n, out_h, out_w, buf, fmt, h, w, table, alpha, layout)
+
+    def labels_overlay_yuv_device(self, src_ptr, dst_ptr, n, out_h, out_w, layout, table, alpha=128):
+        """the same from frames in HBM into caller-owned HBM of the same layout (`layout`: a utils.image.overlay_layout dict or a YUVLayout);
+        dst_ptr == src_ptr blends in place, any other overlap is refused.  Enqueued, no host wait"""
+        self._overlay_yuv_device(lib().accel_model_labels_overlay_yuv, src_ptr, dst_ptr, n, out_h, out_w, layout, table, alpha)
+
+    def scores_overlay_yuv(self, n, out_h, out_w, buf, fmt, h, w, table, alpha=128, **layout):
+        """accel_model_scores_overlay_yuv: labels_overlay_yuv with the labels of the interpolated scores"""
+        return self._overlay_yuv(lib().accel_model_scores_overlay_yuv, n, out_h, out_w, buf, fmt, h, w, table, alpha, layout)
+
+    def scores_overlay_yuv_device(self, src_ptr, dst_ptr, n, out_h, out_w, layout, table, alpha=128):
+        """the same from frames in HBM into caller-owned HBM; dst_ptr == src_ptr blends in place"""
+        self._overlay_yuv_device(lib().accel_model_scores_overlay_yuv, src_ptr, dst_ptr, n, out_h, out_w, layout, table, alpha)
 
     def read_async(self, buf, pinned):
         """enqueue the download of `buf` into a PinnedBuffer on the compute stream; valid after ctx.sync()"""

@@ -664,3 +664,122 @@ def bgr_to_yuv_host(frames, fmt, colour=0, siting="centre"):
     q10 = lambda p: (np.clip(np.rint(p), 0, 1023).astype("<u2") << 6)
     words = np.concatenate([q10(luma).reshape(n, -1), np.stack([q10(cb), q10(cr)], axis=-1).reshape(n, -1)], axis=1)
     return np.ascontiguousarray(words).view(np.uint8).reshape(n, -1)
+
+
+# ---- the overlay in the frame's own format --------------------------------------------------------------------------------------------------------
+# A label map blended over NV12, I420 / YV12, P010 or YUY2 frames and written back as the same format in the same layout (csrc/overlay_yuv.hip):
+# the palette goes to (Y, Cb, Cr) ONCE, on the host, in float64 (palette_ycbcr); everything per sample is integer arithmetic with one rounding
+# (overlay_yuv_host).  The overlay's chroma is the mean of the palette colours over the luma pixels a chroma sample covers -- whatever the siting
+# of the frame's own samples, which are blended where they are and are not resited.
+def palette_ycbcr(palette, colour, bits=8):
+    """A 256 x 3 R, G, B palette as the 256 x 3 uint16 table (Y, Cb, Cr) accel_labels_overlay_yuv takes, in the units of the samples: the float64
+    forward matrix of bgr_to_nv12_host for `colour` (NV12_COLOURS) -- y = kr r + kg g + kb b, Y = yoff + y / ky, Cb = 128 + (b - y) / (2 (1 - kb)) / s,
+    Cr likewise with r and kr -- then rint and a clip to 0 .. 255.  bits=10 (P010): everything before the rounding, the luma offset and the 128
+    included, times 4 in the limited-range modes and times 1023 / 255 in the full-range ones, then rint and a clip to 0 .. 1023 (so a grey is
+    (.., 512, 512) in the limited modes and (.., 514, 514) in the full-range ones: 128 x 1023 / 255 = 513.5)."""
+    if bits not in (8, 10):
+        raise ValueError("bits = %r, must be 8 or 10" % (bits,))
+    p = np.asarray(palette, np.uint8).reshape(-1)
+    if p.size != 768:
+        raise ValueError("the palette must hold 256 x 3 bytes (R, G, B), got %d" % p.size)
+    kr, kg, kb, yoff, ky, s = _nv12_standard(colour)
+    r, g, b = (p.reshape(256, 3)[:, i].astype(np.float64) for i in range(3))
+    y = kr * r + kg * g + kb * b
+    ycc = np.stack([yoff + y / ky, 128.0 + (b - y) / (2.0 * (1.0 - kb)) / s, 128.0 + (r - y) / (2.0 * (1.0 - kr)) / s], axis=1)
+    if bits == 10:
+        ycc = ycc * (4.0 if yoff else 1023.0 / 255.0)
+    return np.clip(np.rint(ycc), 0, (1 << bits) - 1).astype(np.uint16)
+
+
+def overlay_format(fmt):
+    """the number 0 .. 3 of a format an overlay is written in: those of yuv_format, and "nv12" or 3 for NV12"""
+    if (isinstance(fmt, str) and fmt.lower() == "nv12") or (isinstance(fmt, (int, np.integer)) and not isinstance(fmt, bool) and int(fmt) == 3):
+        return 3
+    return yuv_format(fmt)
+
+
+def overlay_layout(fmt, h, w, **layout):
+    """the layout dict of overlay_yuv_host and accel_labels_overlay_yuv: yuv_layout for formats 0 .. 2; for NV12 (format 3) the fields of nv12_layout
+    under the names of the C struct -- pitch, u_offset (the chroma plane; `uv_offset` is accepted too), frame_bytes, pitch_c = v_offset = 0"""
+    f = overlay_format(fmt)
+    if f != 3:
+        return yuv_layout(f, h, w, **layout)
+    layout = dict(layout)
+    uv = layout.pop("u_offset", None)
+    uv = layout.pop("uv_offset", None) if uv is None else uv
+    for field in ("pitch_c", "v_offset"):
+        value = layout.pop(field, None)
+        if value is not None and int(value) != 0:
+            raise ValueError("%s = %d, but NV12 has no such field: it must be 0" % (field, int(value)))
+    lay = nv12_layout(h, w, layout.pop("pitch", None), uv, layout.pop("frame_bytes", None))
+    if layout:
+        raise TypeError("unknown layout keywords for NV12: %s" % ", ".join(sorted(layout)))
+    return dict(format=3, h=lay["h"], w=lay["w"], pitch=lay["pitch"], pitch_c=0, u_offset=lay["uv_offset"], v_offset=0, frame_bytes=lay["frame_bytes"])
+
+
+def overlay_yuv_host(buf, fmt, h, w, labels_at_source, table, alpha, **layout):
+    """The specification of accel_labels_overlay_yuv: the frames in `buf` (I420 / YV12, P010, YUY2 as for yuv_to_bgr_host; "nv12" or 3: NV12 with the
+    keywords pitch, u_offset, frame_bytes) blended with the colours table[label] of `labels_at_source` ([n x] h x w, the labels of the source pixels:
+    labels_to_source_host or labels_interpolated_host) and returned as a uint8 copy of `buf` in which only the samples differ.  `table` is 256 x 3
+    (Y, Cb, Cr) in the units of the samples (palette_ycbcr), a = alpha in 0 .. 256.  Integers, one rounding per sample:
+        luma            Y'  = (a * T[L].Y + (256 - a) * Y + 128) >> 8
+        4:2:0 chroma    Cb' = (a * S + (256 - a) * 4 * Cb + 512) >> 10, S = the sum of T[L].Cb over the sample's 2 x 2 luma pixels; Cr alike
+        4:2:2 chroma    Cb' = (a * S2 + (256 - a) * 2 * Cb + 256) >> 9, S2 over the two pixels of the quad (YUY2)
+        P010            the operands are word >> 6; the stored word is sample << 6
+    The overlay's chroma is the block mean of the table's colours whatever the siting of the frame's samples, which are not resited."""
+    a = int(alpha)
+    if not 0 <= a <= 256:
+        raise ValueError("alpha = %r, must be in 0 .. 256" % (alpha,))
+    lay = overlay_layout(fmt, h, w, **layout)
+    f, h, w, pitch = lay["format"], lay["h"], lay["w"], lay["pitch"]
+    src = np.asarray(buf)
+    if f == 3:
+        flat = np.ascontiguousarray(nv12_bytes(src, dict(frame_bytes=lay["frame_bytes"]))).reshape(-1)
+        n = flat.size // lay["frame_bytes"]
+    else:
+        flat, n = yuv_bytes(src, lay)
+    T = np.asarray(table).astype(np.int64).reshape(-1)
+    top = 1023 if f == 1 else 255
+    if T.size != 768 or T.min() < 0 or T.max() > top:
+        raise ValueError("the table must hold 256 x 3 values (Y, Cb, Cr) in 0 .. %d" % top)
+    T = T.reshape(256, 3)
+    L = np.asarray(labels_at_source)
+    if L.ndim == 2:
+        L = L[None]
+    if L.shape != (n, h, w):
+        raise ValueError("labels of shape %s for %d frames of %d x %d" % (L.shape, n, h, w))
+    out = flat.copy()
+    ia = 256 - a
+    base = (np.arange(n, dtype=np.int64) * lay["frame_bytes"])[:, None, None]
+    ys, xs = np.arange(h, dtype=np.int64)[None, :, None], np.arange(w, dtype=np.int64)[None, None, :]
+    cxs = np.arange(w // 2, dtype=np.int64)[None, None, :]
+    if f == 1:
+        fetch = lambda i: (flat[i].astype(np.int64) | flat[i + 1].astype(np.int64) << 8) >> 6
+        def store(i, v):
+            out[i], out[i + 1] = ((v << 6) & 255).astype(np.uint8), (v >> 2).astype(np.uint8)
+    else:
+        fetch = lambda i: flat[i].astype(np.int64)
+        def store(i, v):
+            out[i] = v.astype(np.uint8)
+    luma = base + ys * pitch + xs * (1 if f in (0, 3) else 2)
+    store(luma, (a * T[L, 0] + ia * fetch(luma) + 128) >> 8)
+    if f == 2:
+        quad = base + ys * pitch + 4 * cxs
+        for ch, at in ((1, quad + 1), (2, quad + 3)):
+            s = T[L, ch].reshape(n, h, w // 2, 2).sum(axis=3)
+            store(at, (a * s + ia * 2 * fetch(at) + 256) >> 9)
+        return out.reshape(src.shape) if src.dtype == np.uint8 else out
+    cys = np.arange(h // 2, dtype=np.int64)[None, :, None]
+    if f == 0:
+        c = base + cys * lay["pitch_c"] + cxs
+        planes = ((1, lay["u_offset"] + c), (2, lay["v_offset"] + c))
+    elif f == 3:
+        c = base + lay["u_offset"] + cys * pitch + 2 * cxs
+        planes = ((1, c), (2, c + 1))
+    else:
+        c = base + lay["u_offset"] + cys * pitch + 4 * cxs
+        planes = ((1, c), (2, c + 2))
+    for ch, at in planes:
+        s = T[L, ch].reshape(n, h // 2, 2, w // 2, 2).sum(axis=(2, 4))
+        store(at, (a * s + ia * 4 * fetch(at) + 512) >> 10)
+    return out.reshape(src.shape) if src.dtype == np.uint8 else out

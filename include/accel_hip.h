@@ -463,6 +463,43 @@ int accel_model_confidence_interp(accel_model* m, int n, int out_h, int out_w, i
                                   uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
                                   uint64_t* hist, int dst_on_device);
 
+/* ---- finished frames: the overlay in the frame's own format ------------------------------------------------------------
+ * The label map blended over NV12, I420 / YV12, P010 or YUY2 frames and written as the same format in the same layout
+ * (csrc/overlay_yuv.hip): what an encoder, a compositor or a capture-card output takes, with no BGR picture in between.
+ * `layout` as for the frame routes, checked by their rules, with format 3 = NV12 as for the _sited entry points (u_offset =
+ * the chroma plane, rows `pitch` apart, pitch_c = v_offset = 0); h x w of the geometry above are layout->h x layout->w.
+ * `layout->colour` is NOT looked at: the colours arrive as palette_ycc, 256 x 3 uint16 (Y, Cb, Cr) per label in the units
+ * of the samples (0 .. 255; 0 .. 1023 for P010), which the caller makes once from an R, G, B palette with the standard's
+ * forward matrix -- accel_amd/utils/image.py palette_ycbcr, INTEGRATION.md has the formula.  With a = alpha in 0 .. 256,
+ * T the table and L(x, y) the label of source pixel (x, y) under the nearest rule above:
+ *   luma            Y'  = (a * T[L(x, y)].Y + (256 - a) * Y + 128) >> 8
+ *   4:2:0 chroma    Cb' = (a * S + (256 - a) * 4 * Cb + 512) >> 10 with S the sum of T[L].Cb over the 2 x 2 luma pixels
+ *                   (2cx .. 2cx + 1, 2cy .. 2cy + 1) of sample (cx, cy); Cr alike                (NV12, I420 / YV12, P010)
+ *   4:2:2 chroma    Cb' = (a * S2 + (256 - a) * 2 * Cb + 256) >> 9 with S2 over the two pixels of the quad; Cr alike  (YUY2)
+ *   P010            the operands are word >> 6; the stored word is sample << 6, its low six bits are zero
+ * Integer arithmetic, one rounding per sample, no clip needed; alpha = 0 returns every sample unchanged.  The overlay's
+ * chroma is the block mean of the palette colours whatever the siting of the frame's own samples, which are blended where
+ * they are and are not resited.  The specification is accel_amd/utils/image.py overlay_yuv_host, bit for bit.
+ * `dst` has the layout of `frame`.  Bytes that are not samples -- between rows, between planes, after a frame -- are never
+ * written in a device `dst`; a host `dst` of (n - 1) * frame_bytes + the extent of a frame bytes holds the input's bytes
+ * there.  A device `dst` may be the device `frame` itself (in place on a decoder's surface); any other overlap of the two
+ * n * frame_bytes ranges is an error.  The samples of a layout must be distinct bytes (I420 planes that interleave row by
+ * row are; planes laid over each other are not, and the result is then undefined).
+ * Argument errors (a NULL frame, dst, palette_ycc or layout, a table entry above 255 -- above 1023 for P010 --, an odd
+ * device address for P010, and those of the layout, the geometry and alpha) return ACCEL_ERR_ARG before anything is
+ * enqueued, with a message that names the argument.
+ *   accel_labels_overlay_yuv         operator level: host labels (n x H x W) and frames in, host bytes out (the parity tests)
+ *   accel_model_labels_overlay_yuv   on the model's `labels` buffer; frame_on_device / dst_on_device as for
+ *                                    accel_model_labels_colour.  It only reads `labels`: no write generation changes
+ *   accel_model_scores_overlay_yuv   the same with the labels of the interpolated scores (accel_model_scores_labels), made
+ *                                    into a library-owned scratch first; it only reads `logits` */
+int accel_labels_overlay_yuv(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, const accel_yuv_layout* layout,
+                             const uint16_t* palette_ycc, int alpha, const uint8_t* frame, uint8_t* dst);
+int accel_model_labels_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
+                                   int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device);
+int accel_model_scores_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
+                                   int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device);
+
 /* whole-frame entry points, the two Predictor.predict calls of the demo loop
  * (demo.py:235-245; tester.py:158-171 im_segment).  img_*: fp32 1x3xHxW already
  * mean-subtracted (lib/utils/image.py:224-235).  Any output pointer may be NULL.
