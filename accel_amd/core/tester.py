@@ -185,12 +185,20 @@ class Predictor(object):
         return self._plans[(N, H, W)]
 
     # -- forward ---------------------------------------------------------------------------------
-    def predict(self, data_batch):
+    def stage(self, data_batch):
+        """Brings the image inputs of `data_batch` into HBM exactly as predict() would and runs nothing: `data_key` (non-key graphs) and `data`
+        are then resident, and a predict() of the same arrays -- by this predictor or by the other one of its pair, which shares the model --
+        finds them there and moves nothing.  What the adaptive key-frame schedule looks at before it chooses the predictor.  Returns the
+        model.  Inputs without a uid (plain numpy) cannot be recognised later: they would be uploaded again by predict()."""
         arrays = dict(zip(self._data_names, data_batch.data[0]))
-        data = arrays["data"]
-        N, _, H, W = tuple(data.shape)
-        plan, lw, m = self._bind((H, W), N)
+        N, _, H, W = tuple(arrays["data"].shape)
+        _, _, m = self._bind((H, W), N)
         self._model = m
+        self._stage_images(m, arrays, N, H, W)
+        return m
+
+    def _stage_images(self, m, arrays, N, H, W):
+        data = arrays["data"]
         # Host->HBM copies are the dominant cost of the reference's per-frame loop (25 MB fp32 per image).  The key
         # graph does not read `data_key`, and on non-key frames `data_key` is the previous call's `data` array
         # (demo.py:176-181 builds it that way).  Arrays are immutable and carry a uid, so "the bytes of this input are
@@ -222,7 +230,15 @@ class Predictor(object):
                 _write_image(m, "data", data)
             res["data"] = tag
         pre.pop("data", None)
-        for name in self._data_names:          # further image inputs (data_ref of the training graphs)
+
+    def predict(self, data_batch):
+        arrays = dict(zip(self._data_names, data_batch.data[0]))
+        data = arrays["data"]
+        N, _, H, W = tuple(data.shape)
+        plan, lw, m = self._bind((H, W), N)
+        self._model = m
+        self._stage_images(m, arrays, N, H, W)
+        for name in self._data_names:        # further image inputs (data_ref of the training graphs)
             if name not in ("data", "data_key", "feat_key") and name in lw.image_vars:
                 m.write(name, _host(arrays[name]))
         if not self._is_key:

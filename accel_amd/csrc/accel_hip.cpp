@@ -820,6 +820,14 @@ static int input_slot(accel_plan* p, const BufRef& r, const float* const** out)
     return 0;
 }
 
+// the frame size a prep kernel reads a whole persistent input buffer at (what accel_model_frame_change looks at)
+static void input_shape(accel_plan* p, const BufRef& r, int H, int W)
+{
+    if (r.space == "A" || r.off != 0) return;
+    DevBuf& b = p->m->pbufs[r.space];
+    b.img_h = H; b.img_w = W;
+}
+
 // the score-resolution map of a plan's tail lives in the model's persistent buffer `scores` (shared by the key and the non-key plan, like `logits`)
 static int scores_buffer(accel_plan* p, Op& op, const ScoreTailParams& q)
 {
@@ -858,6 +866,7 @@ static int finalize_op(accel_plan* p, Op& op)
         if ((rc = resolve(p, op.a, "src")) || (rc = resolve(p, op.b, "dst"))) return rc;
         if ((rc = input_slot(p, op.a, &op.slot_a))) return rc;
         op.H = (int)kv_int(kv, "H"); op.W = (int)kv_int(kv, "W");
+        input_shape(p, op.a, op.H, op.W);
         if (op.b.Cs != 4) return fail(ACCEL_ERR_PLAN, "prep_rgb: dst must be NHWC4");
         if (kv_has(kv, "bn")) {
             std::vector<float> s, b;
@@ -873,6 +882,8 @@ static int finalize_op(accel_plan* p, Op& op)
         if ((rc = resolve(p, op.a, "cur")) || (rc = resolve(p, op.b, "prev")) || (rc = resolve(p, op.c, "dst"))) return rc;
         if ((rc = input_slot(p, op.a, &op.slot_a)) || (rc = input_slot(p, op.b, &op.slot_b))) return rc;
         op.H = (int)kv_int(kv, "H"); op.W = (int)kv_int(kv, "W");
+        input_shape(p, op.a, op.H, op.W);
+        input_shape(p, op.b, op.H, op.W);
         if (op.c.Cs != 8 || (op.H & 1) || (op.W & 1)) return fail(ACCEL_ERR_PLAN, "prep_flow: dst must be NHWC8 and H,W even");
         return 0;
     }

@@ -1,6 +1,6 @@
 // libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
 // points behind them -- uint8, NV12, I420, P010 and YUY2 frames in, finished frames, confidence (of stored and of interpolated scores), interpolated labels and
-// the overlay in the frame's own format out (see include/accel_hip.h).  Nothing here knows about plans.
+// the overlay in the frame's own format out, and the frame-change measure of an image input (see include/accel_hip.h).  Nothing here knows about plans.
 #include <cstring>
 
 #include "accel_objects.h"
@@ -1304,6 +1304,139 @@ extern "C" int accel_model_scores_overlay_yuv(accel_model* m, int n, int out_h, 
         HIP_TRY(launch_overlay_yuv(lab, n, h, w, h, w, y, palette_ycc, alpha, f, d, st));       // the scratch at the identity geometry
         return 0;
     });
+}
+
+// ---- frame change: the measure behind content-adaptive key frames (frame_change.hip) ------------------------------------------------------------
+// What the two entry points share, checked before anything is enqueued: every message names the argument at fault.  `any_out`: at least one output
+// is given (the model level always writes its current signature).
+static int frame_change_args(const char* fn, int n, int H, int W, int out_h, int out_w, int cell, int level_q, bool has_key, bool any_out,
+                             const void* changed, const void* sad, const void* mask, size_t mask_pitch)
+{
+    const int lim = 32768;
+    if (n < 1 || n > lim) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. %d", fn, n, lim);
+    if (H < 1 || W < 1 || H > lim || W > lim) return fail(ACCEL_ERR_ARG, "%s: H x W = %d x %d, must be in 1 .. %d", fn, H, W, lim);
+    if (out_h < 1 || out_h > H) return fail(ACCEL_ERR_ARG, "%s: out_h = %d, must be in 1 .. H = %d", fn, out_h, H);
+    if (out_w < 1 || out_w > W) return fail(ACCEL_ERR_ARG, "%s: out_w = %d, must be in 1 .. W = %d", fn, out_w, W);
+    if (cell != 8 && cell != 16 && cell != 32 && cell != 64) return fail(ACCEL_ERR_ARG, "%s: cell = %d, must be 8, 16, 32 or 64", fn, cell);
+    if (level_q < 0 || level_q > 32768) return fail(ACCEL_ERR_ARG, "%s: level_q = %d, must be in 0 .. 32768 (64 per grey level)", fn, level_q);
+    if (!any_out && !changed && !sad && !mask) return fail(ACCEL_ERR_ARG, "%s: sig_out, changed, sad and mask are all NULL: nothing to compute", fn);
+    if (!has_key && (changed || sad || mask))
+        return fail(ACCEL_ERR_ARG, "%s: sig_key is NULL, but %s is asked for: a comparison needs the signature of a key frame", fn,
+                    changed ? "changed" : sad ? "sad" : "mask");
+    const int gw = (out_w + cell - 1) / cell;
+    if (mask && mask_pitch < (size_t)gw) return fail(ACCEL_ERR_ARG, "%s: mask_pitch = %zu bytes, a row of gw = %d cells has %d", fn, mask_pitch, gw, gw);
+    return 0;
+}
+
+// the device side of a comparison whose results go to the host: changed (n words), sad (n words), mask (tight rows of gw bytes), each part 256-byte aligned
+struct ChangeStage {
+    size_t changed = 0, sad = 0, mask = 0, bytes = 0;
+    ChangeStage(int n, int gh, int gw, bool c, bool s, bool m)
+    {
+        auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
+        if (c) changed = take((size_t)n * sizeof(uint32_t));
+        if (s) sad = take((size_t)n * sizeof(uint64_t));
+        if (m) mask = take((size_t)n * gh * gw);
+    }
+};
+
+// the comparison of `img` with `key` into the stage at `base`, its results copied to the host; the call waits
+static int frame_change_to_host(const float* img, const int* key, unsigned char* base, const ChangeStage& cs, int n, int H, int W, int out_h, int out_w,
+                                int cell, int level_q, int* sig_dev, uint32_t* changed, uint64_t* sad, uint8_t* mask, size_t mask_pitch, hipStream_t st)
+{
+    const int gh = (out_h + cell - 1) / cell, gw = (out_w + cell - 1) / cell;
+    unsigned* dc = changed ? reinterpret_cast<unsigned*>(base + cs.changed) : nullptr;
+    unsigned long long* ds = sad ? reinterpret_cast<unsigned long long*>(base + cs.sad) : nullptr;
+    unsigned char* dm = mask ? base + cs.mask : nullptr;
+    HIP_TRY(launch_frame_change(img, key, n, H, W, out_h, out_w, cell, level_q, sig_dev, dc, ds, dm, (size_t)gw, st));
+    if (changed) HIP_TRY(hipMemcpyAsync(changed, dc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (sad) HIP_TRY(hipMemcpyAsync(sad, ds, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (mask) HIP_TRY(rows_to_host(mask, mask_pitch, dm, (size_t)gw, (size_t)n * gh, st));
+    return 0;
+}
+
+extern "C" int accel_frame_change(accel_ctx* ctx, const float* img, const int32_t* sig_key, int n, int H, int W, int out_h, int out_w, int cell, int level_q,
+                                  int32_t* sig_out, uint32_t* changed, uint64_t* sad, uint8_t* mask, size_t mask_pitch)
+{
+    const char* fn = "accel_frame_change";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!img) return fail(ACCEL_ERR_ARG, "%s: img is NULL", fn);
+    if (int rc = frame_change_args(fn, n, H, W, out_h, out_w, cell, level_q, sig_key != nullptr, sig_out != nullptr, changed, sad, mask, mask_pitch)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int gh = (out_h + cell - 1) / cell, gw = (out_w + cell - 1) / cell;
+    const size_t sb = (size_t)n * gh * gw * sizeof(int32_t);
+    DevTemps t;
+    const ChangeStage cs(n, gh, gw, changed, sad, mask);
+    const float* x = static_cast<const float*>(t.upload(img, (size_t)n * 3 * H * W * sizeof(float)));
+    const int* key = sig_key ? static_cast<const int*>(t.upload(sig_key, sb)) : nullptr;
+    int* sig = sig_out ? static_cast<int*>(t.get(sb)) : nullptr;
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!x || !base || (sig_key && !key) || (sig_out && !sig)) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    if (int rc = frame_change_to_host(x, key, base, cs, n, H, W, out_h, out_w, cell, level_q, sig, changed, sad, mask, mask_pitch, ctx->stream)) return rc;
+    if (sig_out) HIP_TRY(hipMemcpyAsync(sig_out, sig, sb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_model_frame_change(accel_model* m, const char* buf, int n, int out_h, int out_w, int cell, int level_q, uint32_t* changed,
+                                        uint64_t* sad, uint8_t* mask, size_t mask_pitch, int dst_on_device, int* compared)
+{
+    const char* fn = "accel_model_frame_change";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!buf) return fail(ACCEL_ERR_ARG, "%s: buf is NULL", fn);
+    if (!compared) return fail(ACCEL_ERR_ARG, "%s: compared is NULL", fn);
+    auto it = m->pbufs.find(buf);
+    if (it == m->pbufs.end()) return fail(ACCEL_ERR_ARG, "%s: unknown buffer '%s'", fn, buf);
+    const DevBuf& b = it->second;
+    if (!b.slot || b.readers != b.prep_readers || b.img_h < 1 || b.img_w < 1)
+        return fail(ACCEL_ERR_ARG, "%s: '%s' is not an image input of the finalized plans (only buffers that prep_rgb / prep_flow alone read hold frames)", fn, buf);
+    const int H = b.img_h, W = b.img_w;
+    if (int rc = frame_change_args(fn, n, H, W, out_h, out_w, cell, level_q, true, true, changed, sad, mask, mask_pitch)) return rc;
+    if ((size_t)n * 3 * H * W * sizeof(float) > b.bytes)
+        return fail(ACCEL_ERR_ARG, "%s: n = %d, the model is bound for a batch of %zu", fn, n, b.bytes / ((size_t)3 * H * W * sizeof(float)));
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(changed) % 4) return fail(ACCEL_ERR_ARG, "%s: changed = %p, device words must be 4-byte aligned", fn, (void*)changed);
+        if (reinterpret_cast<uintptr_t>(sad) % 8) return fail(ACCEL_ERR_ARG, "%s: sad = %p, device words must be 8-byte aligned", fn, (void*)sad);
+    }
+    const int gh = (out_h + cell - 1) / cell, gw = (out_w + cell - 1) / cell;
+    const size_t sb = (size_t)n * gh * gw * sizeof(int32_t);
+    accel_model::FrameSig &cur = m->sig_cur, &kept = m->sig_kept;
+    cur.n = 0;      // (whatever happens below, the old signature is gone)
+    if (int rc = cur.mem.reserve(m->ctx->device, sb)) return rc;
+    hipStream_t st = m->ctx->stream;
+    // a bound input is read where the plans read it (the caller's frame), not the model-owned copy an earlier write left behind
+    const float* img = static_cast<const float*>(b.bound ? b.bound : b.ptr);
+    int* sig = reinterpret_cast<int*>(cur.mem.ptr);
+    const bool cmp = kept.n == n && kept.out_h == out_h && kept.out_w == out_w && kept.cell == cell;
+    const int* key = cmp ? reinterpret_cast<const int*>(kept.mem.ptr) : nullptr;
+    if (!cmp || (!changed && !sad && !mask)) {
+        HIP_TRY(launch_frame_change(img, nullptr, n, H, W, out_h, out_w, cell, level_q, sig, nullptr, nullptr, nullptr, 0, st));
+    } else if (dst_on_device) {
+        HIP_TRY(launch_frame_change(img, key, n, H, W, out_h, out_w, cell, level_q, sig, changed, reinterpret_cast<unsigned long long*>(sad), mask, mask_pitch, st));
+    } else {
+        const ChangeStage cs(n, gh, gw, changed, sad, mask);
+        if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
+        if (int rc = frame_change_to_host(img, key, m->stage_out.ptr, cs, n, H, W, out_h, out_w, cell, level_q, sig, changed, sad, mask, mask_pitch, st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    cur.n = n; cur.out_h = out_h; cur.out_w = out_w; cur.cell = cell;
+    *compared = cmp ? 1 : 0;
+    return 0;
+}
+
+extern "C" int accel_model_frame_keep(accel_model* m)
+{
+    const char* fn = "accel_model_frame_keep";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    accel_model::FrameSig &cur = m->sig_cur, &kept = m->sig_kept;
+    if (!cur.n) return fail(ACCEL_ERR_ARG, "%s: no signature has been made yet (accel_model_frame_change makes one)", fn);
+    const int gh = (cur.out_h + cur.cell - 1) / cur.cell, gw = (cur.out_w + cur.cell - 1) / cur.cell;
+    const size_t sb = (size_t)cur.n * gh * gw * sizeof(int32_t);
+    kept.n = 0;
+    if (int rc = kept.mem.reserve(m->ctx->device, sb)) return rc;
+    HIP_TRY(launch_copy_bytes(cur.mem.ptr, kept.mem.ptr, sb, m->ctx->stream));
+    kept.n = cur.n; kept.out_h = cur.out_h; kept.out_w = cur.out_w; kept.cell = cur.cell;
+    return 0;
 }
 
 extern "C" int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes)

@@ -47,6 +47,7 @@ struct DevBuf {
     const void** slot = nullptr;
     const void* bound = nullptr;        // what the slot points at when it is not `ptr`
     int readers = 0, prep_readers = 0;  // plan operands resolved to this buffer / those of prep_rgb and prep_flow
+    int img_h = 0, img_w = 0;           // an image input: the H x W its prep kernels read it at (bytes / (3 * H * W * 4) frames)
 };
 
 // device bytes that grow on demand and are kept otherwise.  A buffer that is too small is released with hipFree, which waits for the device: no
@@ -106,6 +107,13 @@ struct accel_model {
     // accel_model_scores_hist_add / _scores_colour: the labels of the interpolated scores at the source size (n x h x w uint8, tight rows)
     // on their way to the counting / colouring kernel
     DevScratch interp_labels;
+    // accel_model_frame_change / accel_model_frame_keep: the signature of the frame looked at last and the one kept at the last key frame
+    // (n x gh x gw int32 each, allocated on first use), with the geometry they were made under (n = 0: none yet)
+    struct FrameSig {
+        DevScratch mem;
+        int n = 0, out_h = 0, out_w = 0, cell = 0;
+    };
+    FrameSig sig_cur, sig_kept;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;

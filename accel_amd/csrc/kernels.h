@@ -215,6 +215,13 @@ hipError_t launch_scores_labels(const float* scores, int n, int ncls, int H, int
 hipError_t launch_scores_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
                                     unsigned char* labels, size_t labels_pitch, unsigned char* conf, size_t conf_pitch, float* margin, size_t margin_pitch,
                                     unsigned char* second, size_t second_pitch, unsigned long long* hist, hipStream_t st);
+// frame change (frame_change.hip): the image input img (n x 3 x H x W fp32, planes R, G, B, valid region out_h x out_w) -> its signature, n x gh x gw
+// int32 sums of 2 qR + 5 qG + qB over cells of cell x cell pixels (gh = ceil(out_h / cell), gw alike; q = rint(clamp(x, +-512) * 8)), and, against
+// the signature sig_key of a key frame (null: signature only), per frame changed = the cells with |S - S_key| > level_q * area, sad = the sum of the
+// differences (both overwritten), mask = 1 per changed cell (rows mask_pitch bytes apart): utils/image.py frame_signature_host / frame_change_host.
+// A null output is left out, at least one is given.  Device pointers; the kernel only reads `img` and `sig_key`
+hipError_t launch_frame_change(const float* img, const int* sig_key, int n, int H, int W, int out_h, int out_w, int cell, int level_q, int* sig_out,
+                               unsigned* changed, unsigned long long* sad, unsigned char* mask, size_t mask_pitch, hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

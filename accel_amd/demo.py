@@ -139,6 +139,7 @@ class ClipRunner(object):
                                        provide_data=provide, provide_label=[None],
                                        arg_params=arg_params, aux_params=aux_params, model=model, owner=self.owner)
         self.feat = None
+        self.last_key, self.last_change = None, None      # what the last step did (see step)
         self.output_key = 'croped_score_output' if self.version in ('101', 'dff') else 'correction_output'
 
     def close(self):
@@ -151,12 +152,44 @@ class ClipRunner(object):
         """start the upload of the NEXT frame's image (page-locked arrays only) beside the running forward"""
         return self.key_predictor.prefetch(arrays[0])
 
-    def step(self, idx, arrays, interval):
-        """One frame (demo.py:235-245).  Returns (logits handle, label-map handle)."""
+    def _decide(self, idx, arrays, batch, schedule):
+        """With a schedule: the images are staged into HBM (Predictor.stage: what predict() would do, so the predictor chosen afterwards moves
+        nothing), `data` is measured against the frame kept at the last key frame (accel_model_frame_change) when the schedule looks at frames,
+        the schedule decides, and on a key frame the frame's signature becomes the kept one."""
+        self.last_change = None
+        if not schedule.needs_change:
+            return schedule.decide(idx)
+        for name, a in zip(self.data_names[:2], arrays[:2]):
+            if getattr(a, "uid", None) is None:
+                raise ValueError("the adaptive schedule stages the frame before it chooses a predictor, and `%s` is an array without identity "
+                                 "(plain numpy): it could not be recognised as staged and would be uploaded twice; wrap it with mx.nd.array / "
+                                 "mx.nd.raw_frames" % name)
+        data = arrays[0]
+        m = self.cur_predictor.stage(batch)
+        n, H, W = data.shape[0], data.shape[2], data.shape[3]
+        g = getattr(data, "geometry", None)      # raw frames: the valid region inside the padded size
+        out_h, out_w = (g["out_h"], g["out_w"]) if g else (H, W)
+        got = m.frame_change("data", n, out_h, out_w, schedule.cell, schedule.level_q)
+        if got is not None:
+            cells = (-(-out_h // schedule.cell)) * (-(-out_w // schedule.cell))
+            self.last_change = [(int(c), cells, int(s)) for c, s in zip(got[0], got[1])]
+        key = schedule.decide(idx, self.last_change)
+        if key:
+            m.frame_keep()
+        return key
+
+    def step(self, idx, arrays, interval, schedule=None):
+        """One frame (demo.py:235-245).  Returns (logits handle, label-map handle).  schedule=None: a key frame at idx % interval == 0, the
+        reference's loop; a core.schedule.KeySchedule decides otherwise (`interval` is then not looked at) and `last_key` / `last_change`
+        (per frame (changed cells, cells, sad), or None where nothing was compared) say what happened."""
         batch = mx.io.DataBatch(data=[list(arrays)], label=[], pad=0, index=idx,
                                 provide_data=[[(k, v.shape) for k, v in zip(self.data_names, arrays)]],
                                 provide_label=[None])
-        if idx % interval == 0:
+        if schedule is not None:
+            self.last_key = self._decide(idx, arrays, batch, schedule)
+        else:
+            self.last_key = idx % interval == 0
+        if self.last_key:
             output_all, self.feat = im_segment(self.key_predictor, batch)
             logits = output_all[0]['croped_score_output']
         else:
@@ -226,6 +259,13 @@ def main(argv=None):
                     help='with --finish-on-gpu and --nv12 or --yuv: the labels blended over the frame IN ITS OWN FORMAT on the GPU (what an '
                          'encoder or a compositor takes; honours --interpolate); --out writes overlay_<frame>.png, the GPU\'s BGR '
                          'conversion of those bytes')
+    ap.add_argument('--adaptive-key', dest='adaptive_key', type=float, default=None, metavar='SHARE',
+                    help='content-adaptive key frames: a frame becomes a key frame when more than SHARE (0 .. 1) of its cells changed against '
+                         'the last key frame, measured on the GPU where the frame is; --interval is then the LONGEST distance between key '
+                         'frames.  The per-frame line gains " key" / " share 0.xxx"')
+    ap.add_argument('--key-level', dest='key_level', type=float, default=16.0,
+                    help='with --adaptive-key: the mean absolute change of a cell, in grey levels, above which it counts as changed')
+    ap.add_argument('--key-cell', dest='key_cell', type=int, default=32, choices=[8, 16, 32, 64], help='with --adaptive-key: the cell size in pixels')
     ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
                                                  '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
@@ -306,11 +346,15 @@ def main(argv=None):
     for j in range(min(2, len(data))):       # warm up (demo.py:207-220)
         runner.step(j, data[j], interv)[1].asnumpy()
     print("warmup done")
+    schedule = None
+    if args.adaptive_key is not None:
+        from .core.schedule import KeySchedule
+        schedule = KeySchedule.adaptive(args.adaptive_key, level=args.key_level, cell=args.key_cell, max_interval=interv)
     time_sum, count = 0.0, 0
     hist = np.zeros((num_classes, num_classes))
     for idx, arrays in enumerate(data):
         tic()
-        lg, lab = runner.step(idx, arrays, interv)
+        lg, lab = runner.step(idx, arrays, interv, schedule=schedule)
         if idx + 1 < len(data) and not args.pageable:
             runner.prefetch(data[idx + 1])        # next frame starts crossing PCIe while this one computes
         fused = args.finish_on_gpu and args.interpolate and args.confidence       # labels, conf and hist from ONE pass over the logits
@@ -324,7 +368,12 @@ def main(argv=None):
         elapsed = toc()
         time_sum += elapsed
         count += 1
-        print('testing {} {:.4f}s [{:.4f}s]'.format(names[idx], elapsed, time_sum / count))
+        note = ''
+        if schedule is not None:
+            note = ' key' if runner.last_key else ''
+            if runner.last_change:
+                note += ' share {:.3f}'.format(max(c / float(cells) for c, cells, _ in runner.last_change))
+        print('testing {} {:.4f}s [{:.4f}s]{}'.format(names[idx], elapsed, time_sum / count, note))
         if args.confidence:       # after the clock: the histogram is 2 KB, the map a byte per source pixel
             if not fused:
                 conf, conf_hist = results.confidence(lg, source, hist=True)

@@ -112,6 +112,9 @@ def _declare(lib):
         "accel_model_scores_labels": [vp, i, i, i, i, i, vp, sz, i],
         "accel_model_scores_hist_add": [vp, vp, i, i, i, sz, i, i, i, i],
         "accel_model_scores_colour": [vp, i, i, i, i, i, vp, i, vp, sz, i, i, vp, sz, i],
+        "accel_frame_change": [vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, sz],
+        "accel_model_frame_change": [vp, c.c_char_p, i, i, i, i, i, vp, vp, vp, sz, i, c.POINTER(c.c_int)],
+        "accel_model_frame_keep": [vp],
         "accel_labels_overlay_yuv": [vp, vp, i, i, i, i, i, c.POINTER(YUVLayout), vp, i, vp, vp],
         "accel_model_labels_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
         "accel_model_scores_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
@@ -610,6 +613,34 @@ class Context(object):
         check(lib().accel_scores_labels(self.handle, _fp(a), n, ncls, H, W, int(out_h), int(out_w), int(h), int(w), _fp(out), pitch))
         return out
 
+    def frame_change(self, x, out_h, out_w, cell, level_q=0, sig_key=None, sig=True, changed=True, sad=True, mask=True):
+        """accel_frame_change: the image input x (n x 3 x H x W fp32, valid region out_h x out_w) -> (sig, changed, sad, mask) -- its signature
+        (n x gh x gw int32) and, against the signature `sig_key` of a key frame, the number of changed cells (n uint32), the sum of the
+        differences (n uint64) and the mask (utils.image.frame_signature_host / frame_change_host).  sig / changed / sad are True or False
+        (left out: None is returned in its place); mask True, False or an array of n x gh x pitch bytes to write the rows into.
+        sig_key=None: the signature only -- (sig, None, None, None)"""
+        a = _f32(x)
+        if a.ndim != 4 or a.shape[1] != 3:
+            raise ValueError("x must be n x 3 x H x W fp32, got shape %s" % (a.shape,))
+        n, _, H, W = a.shape
+        cell = int(cell)
+        gh, gw = -(-int(out_h) // cell) if cell > 0 else 0, -(-int(out_w) // cell) if cell > 0 else 0
+        key = None
+        if sig_key is None:
+            changed = sad = mask = False
+        else:
+            key = np.ascontiguousarray(sig_key, dtype=np.int32)
+            if key.shape != (n, gh, gw):
+                raise ValueError("sig_key of shape %s for %d frames of %d x %d cells" % (key.shape, n, gh, gw))
+        s = np.empty((n, gh, gw), np.int32) if sig else None
+        c = np.zeros(n, np.uint32) if changed else None
+        d = np.zeros(n, np.uint64) if sad else None
+        mk, pitch = (None, 0) if mask is None or mask is False else _result_rows(None if mask is True else mask, n, gh, gw, 1)
+        opt = lambda v: None if v is None else _fp(v)
+        check(lib().accel_frame_change(self.handle, _fp(a), opt(key), n, H, W, int(out_h), int(out_w), cell, int(level_q), opt(s), opt(c), opt(d),
+                                       opt(mk), pitch))
+        return s, c, d, mk
+
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
         _, _, H, W = cur.shape
@@ -1008,6 +1039,38 @@ class Model(object):
         check(lib().accel_model_confidence_interp(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(bool(is_prob)),
                                                   vp(labels_ptr), int(labels_pitch), vp(conf_ptr), int(conf_pitch), vp(margin_ptr), int(margin_pitch),
                                                   vp(second_ptr), int(second_pitch), vp(hist_ptr), 1))
+
+    # ---- frame change: it only READS the image input ---------------------------------------------------------------------------
+    def frame_change(self, buf, n, out_h, out_w, cell, level_q, mask=False):
+        """accel_model_frame_change: the signature of the first n frames of the image input `buf` (what the plans would read: a bound frame
+        included) becomes the model's CURRENT signature and is compared with the KEPT one (frame_keep) if that was made under the same
+        (n, out_h, out_w, cell): -> (changed n uint32, sad n uint64[, mask n x gh x gw uint8]) as numpy arrays, or None where nothing was
+        compared.  It only READS `buf`"""
+        n, cell = int(n), int(cell)
+        c, d = np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        mk, pitch = (None, 0)
+        if mask and cell > 0:
+            mk = np.zeros((n, -(-int(out_h) // cell), -(-int(out_w) // cell)), np.uint8)
+            pitch = mk.shape[2]
+        compared = ctypes.c_int(0)
+        check(lib().accel_model_frame_change(self.handle, buf.encode(), n, int(out_h), int(out_w), cell, int(level_q), _fp(c), _fp(d),
+                                             None if mk is None else _fp(mk), pitch, 0, ctypes.byref(compared)))
+        if not compared.value:
+            return None
+        return (c, d, mk) if mask else (c, d)
+
+    def frame_change_device(self, buf, n, out_h, out_w, cell, level_q, changed_ptr=None, sad_ptr=None, mask_ptr=None, mask_pitch=0):
+        """the same into caller-owned HBM (enqueued, no host wait): n uint32, n uint64 and n x gh rows of mask_pitch bytes; -> whether the kept
+        signature was compared with (the destinations are written only then)"""
+        vp = lambda v: ctypes.c_void_p(v) if v else None
+        compared = ctypes.c_int(0)
+        check(lib().accel_model_frame_change(self.handle, buf.encode(), int(n), int(out_h), int(out_w), int(cell), int(level_q), vp(changed_ptr),
+                                             vp(sad_ptr), vp(mask_ptr), int(mask_pitch), 1, ctypes.byref(compared)))
+        return bool(compared.value)
+
+    def frame_keep(self):
+        """accel_model_frame_keep: the current signature (the last frame_change) becomes the kept one, the one later frames are compared with"""
+        check(lib().accel_model_frame_keep(self.handle))
 
     # ---- labels from interpolated scores: they only READ `logits` ------------------------------------------------------------
     def scores_labels(self, n, out_h, out_w, h, w, out=None):

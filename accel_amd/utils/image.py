@@ -783,3 +783,71 @@ def overlay_yuv_host(buf, fmt, h, w, labels_at_source, table, alpha, **layout):
         s = T[L, ch].reshape(n, h // 2, 2, w // 2, 2).sum(axis=(2, 4))
         store(at, (a * s + ia * 4 * fetch(at) + 512) >> 10)
     return out.reshape(src.shape) if src.dtype == np.uint8 else out
+
+
+# ---- frame change: the measure behind content-adaptive key frames (csrc/frame_change.hip restates both functions bit for bit) ----------------
+FRAME_CELLS = (8, 16, 32, 64)
+
+
+def frame_cells(out_h, out_w, cell):
+    """(gh, gw): the grid of cell x cell cells that covers a valid region of out_h x out_w pixels; the last row / column of cells may be smaller"""
+    cell = int(cell)
+    if cell not in FRAME_CELLS:
+        raise ValueError("cell = %r, must be one of %s" % (cell, ", ".join(str(c) for c in FRAME_CELLS)))
+    return -(-int(out_h) // cell), -(-int(out_w) // cell)
+
+
+def frame_cell_areas(out_h, out_w, cell):
+    """gh x gw int64: the number of valid pixels of every cell"""
+    gh, gw = frame_cells(out_h, out_w, cell)
+    hs = np.minimum(cell, int(out_h) - cell * np.arange(gh, dtype=np.int64))
+    ws = np.minimum(cell, int(out_w) - cell * np.arange(gw, dtype=np.int64))
+    return hs[:, None] * ws[None, :]
+
+
+def frame_level_q(level):
+    """the public `level` (grey levels of mean absolute change per pixel of a cell) in the kernel's units, 64 per grey level"""
+    q = int(round(float(level) * 64))
+    if not 0 <= q <= 32768:
+        raise ValueError("level = %r, must be in 0 .. 512 grey levels" % (level,))
+    return q
+
+
+def frame_signature_host(x, out_h, out_w, cell):
+    """The specification of the signature half of accel_frame_change.  `x` is the image input, n x 3 x H x W fp32 (planes R, G, B, mean-subtracted,
+    padded), of which only the valid region out_h x out_w in the top-left corner is looked at.  Integers throughout:
+        q = int(rint(fmin(fmax(x, -512), 512) * 8))     fp32, round half to even; C fmaxf / fminf: NaN gives -4096, +-inf gives +-4096
+        v = 2 qR + 5 qG + qB                            64 units per grey level
+        S[cy][cx] = the sum of v over the valid pixels of cell (cy, cx)
+    -> n x gh x gw int32 (|S| <= 64 * 64 * 8 * 4096 = 2^27)."""
+    x = np.asarray(x, np.float32)
+    if x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError("x must be n x 3 x H x W fp32, got shape %s" % (x.shape,))
+    n, _, H, W = x.shape
+    out_h, out_w = int(out_h), int(out_w)
+    if not (1 <= out_h <= H and 1 <= out_w <= W):
+        raise ValueError("out_h x out_w = %d x %d, must be in 1 x 1 .. H x W = %d x %d" % (out_h, out_w, H, W))
+    gh, gw = frame_cells(out_h, out_w, cell)
+    valid = x[:, :, :out_h, :out_w]
+    clamped = np.fmin(np.fmax(valid, np.float32(-512.0)), np.float32(512.0))
+    q = np.rint(clamped * np.float32(8.0)).astype(np.int64)
+    v = 2 * q[:, 0] + 5 * q[:, 1] + q[:, 2]
+    full = np.zeros((n, gh * cell, gw * cell), np.int64)
+    full[:, :out_h, :out_w] = v
+    return full.reshape(n, gh, cell, gw, cell).sum(axis=(2, 4)).astype(np.int32)
+
+
+def frame_change_host(sig, sig_key, out_h, out_w, cell, level_q):
+    """The specification of the comparing half of accel_frame_change: two signatures (frame_signature_host) of the same geometry, frame i with frame
+    i.  Per cell d = |S - S_key| and the cell is CHANGED iff d > level_q * area (strict, int64; area = its valid pixels).  Returns per frame
+    (changed uint32: the number of changed cells, sad uint64: the sum of d, mask n x gh x gw uint8: 1 where a cell changed)."""
+    level_q = int(level_q)
+    if not 0 <= level_q <= 32768:
+        raise ValueError("level_q = %d, must be in 0 .. 32768" % level_q)
+    a, b = np.asarray(sig).astype(np.int64), np.asarray(sig_key).astype(np.int64)
+    gh, gw = frame_cells(out_h, out_w, cell)
+    if a.ndim != 3 or a.shape[1:] != (gh, gw) or a.shape != b.shape:
+        raise ValueError("signatures of shapes %s and %s for a grid of %d x %d cells" % (a.shape, b.shape, gh, gw))
+    d = np.abs(a - b)
+    mask = d > level_q * frame_cell_areas(out_h, out_w, cell)[None]
+    return mask.sum(axis=(1, 2)).astype(np.uint32), d.sum(axis=(1, 2)).astype(np.uint64), mask.astype(np.uint8)

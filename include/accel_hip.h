@@ -463,6 +463,47 @@ int accel_model_confidence_interp(accel_model* m, int n, int out_h, int out_w, i
                                   uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
                                   uint64_t* hist, int dst_on_device);
 
+/* ---- frame change: the measure behind content-adaptive key frames ------------------------------------------------------
+ * How much a frame differs from the frame kept at the last key frame, made where every input route (fp32, BGR bytes, NV12,
+ * I420, P010, YUY2, a zero-copy binding) leaves the frame: the image input, n x 3 x H x W fp32, planes R, G, B,
+ * mean-subtracted, of which the valid region out_h x out_w in the top-left corner is looked at and nothing else is read
+ * (csrc/frame_change.hip).  Integer arithmetic; the specification is accel_amd/utils/image.py frame_signature_host /
+ * frame_change_host and the kernel equals it bit for bit.  With cell in {8, 16, 32, 64}, gh = ceil(out_h / cell) and
+ * gw = ceil(out_w / cell):
+ *   q        int(rint(fmin(fmax(x, -512), 512) * 8)), fp32 round-half-to-even; NaN gives -4096, +-inf gives +-4096
+ *   v        2 qR + 5 qG + qB per pixel: 64 units per grey level
+ *   sig      n x gh x gw int32   the SIGNATURE: S = the sum of v over the valid pixels of the cell (|S| <= 2^27)
+ * and against the signature sig_key of another frame (frame i with frame i), per cell d = |S - S_key| and the cell is CHANGED
+ * iff d > level_q * area (strict, 64-bit; area = the valid pixels of the cell: edge cells are smaller; level_q in
+ * 0 .. 32768, 64 per grey level of mean absolute change):
+ *   changed  n uint32            the number of changed cells of the frame (changed / (gh * gw) is the share)
+ *   sad      n uint64            the sum of d over the cells (sad / (64 * out_h * out_w) is the mean absolute change per pixel)
+ *   mask     n x gh x gw uint8   1 where a cell changed; rows `mask_pitch` bytes apart (>= gw), gh * mask_pitch from frame to
+ *                                frame; bytes between rows are not written
+ * changed and sad are OVERWRITTEN; being integer sums they are exact and independent of the order of arrival.  A NULL output
+ * is left out.  Sizes are at most 32768.  Argument errors (a NULL input, a size < 1 or > 32768, out_h > H, out_w > W, a cell
+ * other than 8 / 16 / 32 / 64, level_q outside 0 .. 32768, all outputs NULL, a result asked for without a key, a mask pitch
+ * smaller than a row, n larger than the bound batch, a buffer that is not an image input) return ACCEL_ERR_ARG before
+ * anything is enqueued, with a message that names the argument.
+ *   accel_frame_change          operator level: host image (and key signature) in, host results out (the parity tests).
+ *                               sig_key = NULL: the signature only -- asking for changed, sad or mask is then an error
+ *   accel_model_frame_change    on the image input `buf` (`data` or `data_key`; H, W as the bound plans read it) of a model,
+ *                               enqueued on the context stream.  What is read is what the plans would read: the frame bound
+ *                               with accel_model_bind_device if there is one.  It only reads `buf`: no write generation
+ *                               changes, no captured graph is touched.  It writes the model-owned CURRENT signature (allocated
+ *                               on first use, freed with the model) and compares it with the model's KEPT signature if one
+ *                               exists that was made under the same (n, out_h, out_w, cell): *compared is then 1 and the
+ *                               results are written -- host destinations (dst_on_device = 0) are filled when the call
+ *                               returns, device destinations (= 1: all of them, changed 4-byte and sad 8-byte aligned) when
+ *                               the stream reaches them.  Otherwise *compared is 0 and the result pointers are not written
+ *   accel_model_frame_keep      the current signature becomes the kept one: a stream-ordered copy inside HBM of gh * gw words
+ *                               per frame.  An argument error while no signature has been made */
+int accel_frame_change(accel_ctx* ctx, const float* img, const int32_t* sig_key /* NULL: signature only */, int n, int H, int W, int out_h, int out_w,
+                       int cell, int level_q, int32_t* sig_out, uint32_t* changed, uint64_t* sad, uint8_t* mask, size_t mask_pitch);
+int accel_model_frame_change(accel_model* m, const char* buf, int n, int out_h, int out_w, int cell, int level_q, uint32_t* changed, uint64_t* sad,
+                             uint8_t* mask, size_t mask_pitch, int dst_on_device, int* compared);
+int accel_model_frame_keep(accel_model* m);
+
 /* ---- finished frames: the overlay in the frame's own format ------------------------------------------------------------
  * The label map blended over NV12, I420 / YV12, P010 or YUY2 frames and written as the same format in the same layout
  * (csrc/overlay_yuv.hip): what an encoder, a compositor or a capture-card output takes, with no BGR picture in between.
