@@ -5,7 +5,9 @@ accel_model_confidence), or as labels of their own: `interpolate=True` takes the
 source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour), and
 `confidence(..., interpolate=True)` takes the confidence from those interpolated scores too, with the labels if asked, in one pass
 (csrc/scores_confidence.hip behind accel_model_confidence_interp).  `overlay` blends the labels over NV12 / I420 / P010 / YUY2 frames and
-hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).
+hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).  `summary` says what
+is in the frame, where, and whether it just changed: per-class areas, coordinate sums and boxes, and the class transitions against the
+previous frame, which is kept in HBM (csrc/labels_summary.hip behind accel_model_labels_summary / _scores_summary / _labels_forget).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -14,9 +16,12 @@ camera's h x w, and `RawFrames.geometry` says how to get back.
 
 A label handle names a buffer, not a copy: its `device_ref` is (model, "labels", write generation).  Every function here checks that
 generation first -- stale labels are never read."""
+import collections
+
 import numpy as np
 
 from .. import runtime
+from ..utils.image import summary_centroids, summary_churn  # noqa: F401  (re-exported: the host helpers of `summary`)
 
 
 def _geometry(handle, like, hw=None, scores=False):
@@ -140,6 +145,34 @@ def confidence(handle, like, margin=False, second=False, hist=False, probabiliti
         out = m.confidence(n, out_h, out_w, h, w, **want)
     out = tuple(a for a in out if a is not None)
     return out[0] if len(out) == 1 else out
+
+
+Summary = collections.namedtuple("Summary", "stats box trans")
+
+
+def summary(handle, like, ncls=19, track=False, interpolate=False, box=True):
+    """What is in the frame, where, and did it just change, from the labels of `handle` at the source frames' size without fetching them:
+    Summary(stats, box, trans) -- stats n x ncls x 3 uint64 = (area, sum_x, sum_y) per frame and class (summary_centroids gives the
+    centroids, area / (h * w) the share of the frame), box n x ncls x 4 int32 = the inclusive (x0, y0, x1, y1) of every class, (w, h, -1, -1)
+    for an absent one (None with box=False), ids >= ncls ignored (utils.image.labels_summary_host, on the GPU: csrc/labels_summary.hip).
+    track=True also compares with the previous tracked frame of the same model, kept at the source size in HBM: trans is n x (ncls * ncls)
+    uint64, rows the previous frame's class, columns this frame's (summary_churn gives the churn, per_class_iu of the square matrix the
+    temporal IoU) -- or None where there was nothing to compare with: the first tracked frame, after forget(), or after a change of frame
+    size, batch or ncls.  interpolate=True: `handle` is the LOGITS handle and the labels are those of
+    labels_at_source(handle, like, interpolate=True)."""
+    m = _model(handle, "logits" if interpolate else "labels")
+    n, out_h, out_w, h, w = _geometry(handle, like, scores=bool(interpolate))
+    run = m.scores_summary if interpolate else m.labels_summary
+    return Summary(*run(n, out_h, out_w, h, w, int(ncls), track=bool(track), stats=True, box=bool(box)))
+
+
+def forget(handle):
+    """Drop the map that summary(..., track=True) keeps in the model of `handle` (a label or a logits handle, stale or not: nothing of it
+    is read): call it at the start of a clip or after a cut, so that the first frame is not compared with the last one of another scene."""
+    ref = getattr(handle, "device_ref", None)
+    if not ref:
+        raise runtime.AccelError("not a handle of the GPU path: there is no kept map to forget")
+    ref[0].labels_forget()
 
 
 def confidence_summary(hist, level=128):

@@ -1,6 +1,6 @@
 // libaccel_hip: bytes in and out of a model's persistent buffers (bind, write, read, prefetch and commit), and the frame and result entry
 // points behind them -- uint8, NV12, I420, P010 and YUY2 frames in, finished frames, confidence (of stored and of interpolated scores), interpolated labels and
-// the overlay in the frame's own format out, and the frame-change measure of an image input (see include/accel_hip.h).  Nothing here knows about plans.
+// the overlay in the frame's own format and the per-class summary out, and the frame-change measure of an image input (see include/accel_hip.h).  Nothing here knows about plans.
 #include <cstring>
 
 #include "accel_objects.h"
@@ -1436,6 +1436,152 @@ extern "C" int accel_model_frame_keep(accel_model* m)
     if (int rc = kept.mem.reserve(m->ctx->device, sb)) return rc;
     HIP_TRY(launch_copy_bytes(cur.mem.ptr, kept.mem.ptr, sb, m->ctx->stream));
     kept.n = cur.n; kept.out_h = cur.out_h; kept.out_w = cur.out_w; kept.cell = cur.cell;
+    return 0;
+}
+
+// ---- summary of finished frames: areas, coordinate sums, boxes and class transitions (labels_summary.hip) --------------------------------------
+// What the three entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int summary_args(const char* fn, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls)
+{
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    return ncls_arg(fn, ncls);
+}
+
+// the device side of a summary whose results go to the host: stats (n x ncls x 3 words), box (n x ncls x 4), trans (n x ncls x ncls), each part 256-byte aligned
+struct SummaryStage {
+    size_t stats = 0, box = 0, trans = 0, bytes = 0, sb, bb, tb;
+    SummaryStage(int n, int ncls, bool s, bool b, bool t)
+        : sb((size_t)n * ncls * 3 * sizeof(uint64_t)), bb((size_t)n * ncls * 4 * sizeof(int32_t)), tb((size_t)n * ncls * ncls * sizeof(uint64_t))
+    {
+        auto take = [&](size_t b_) { const size_t at = bytes; bytes += (b_ + 255) / 256 * 256; return at; };
+        if (s) stats = take(sb);
+        if (b) box = take(bb);
+        if (t) trans = take(tb);
+        if (!bytes) bytes = 256;
+    }
+};
+
+// the summary of `labels` into the stage at `base`, its results copied to the host; the caller waits
+static int summary_to_host(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, const unsigned char* prev,
+                           size_t prev_pitch, unsigned char* base, const SummaryStage& ss, uint64_t* stats, int32_t* box, uint64_t* trans, unsigned char* kept,
+                           size_t kept_pitch, hipStream_t st)
+{
+    unsigned long long* ds = stats ? reinterpret_cast<unsigned long long*>(base + ss.stats) : nullptr;
+    int* db = box ? reinterpret_cast<int*>(base + ss.box) : nullptr;
+    unsigned long long* dt = trans ? reinterpret_cast<unsigned long long*>(base + ss.trans) : nullptr;
+    HIP_TRY(launch_labels_summary(labels, n, H, W, out_h, out_w, h, w, ncls, prev, prev_pitch, ds, db, dt, kept, kept_pitch, st));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, ds, ss.sb, hipMemcpyDeviceToHost, st));
+    if (box) HIP_TRY(hipMemcpyAsync(box, db, ss.bb, hipMemcpyDeviceToHost, st));
+    if (trans) HIP_TRY(hipMemcpyAsync(trans, dt, ss.tb, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+extern "C" int accel_labels_summary(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls,
+                                    const uint8_t* prev, size_t prev_pitch, uint64_t* stats, int32_t* box, uint64_t* trans, uint8_t* kept_out,
+                                    size_t kept_pitch)
+{
+    const char* fn = "accel_labels_summary";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (int rc = summary_args(fn, n, H, W, out_h, out_w, h, w, ncls)) return rc;
+    if (!stats && !box && !trans && !kept_out) return fail(ACCEL_ERR_ARG, "%s: stats, box, trans and kept_out are all NULL: nothing to compute", fn);
+    if (trans && !prev) return fail(ACCEL_ERR_ARG, "%s: prev is NULL, but trans is asked for: transitions need the previous frame's labels", fn);
+    if (prev) if (int rc = pitch_arg(fn, "prev_pitch", prev_pitch, w, 1)) return rc;
+    if (kept_out) if (int rc = pitch_arg(fn, "kept_pitch", kept_pitch, w, 1)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const SummaryStage ss(n, ncls, stats, box, trans);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* p = prev && trans ? static_cast<const unsigned char*>(t.upload(prev, (size_t)n * h * prev_pitch)) : nullptr;
+    unsigned char* k = kept_out ? static_cast<unsigned char*>(t.get((size_t)n * h * w)) : nullptr;
+    unsigned char* base = static_cast<unsigned char*>(t.get(ss.bytes));
+    if (!l || !base || (prev && trans && !p) || (kept_out && !k)) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    if (int rc = summary_to_host(l, n, H, W, out_h, out_w, h, w, ncls, p, prev_pitch, base, ss, stats, box, trans, k, (size_t)w, ctx->stream)) return rc;
+    if (kept_out) HIP_TRY(rows_to_host(kept_out, kept_pitch, k, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// what the two model-level forms are told besides the geometry
+static int model_summary_args(const char* fn, int track, const void* stats, const void* box, const void* trans, int dst_on_device, const int* compared)
+{
+    if (!compared) return fail(ACCEL_ERR_ARG, "%s: compared is NULL", fn);
+    if (!stats && !box && !trans) return fail(ACCEL_ERR_ARG, "%s: stats, box and trans are all NULL: nothing to compute", fn);
+    if (trans && !track) return fail(ACCEL_ERR_ARG, "%s: trans is asked for with track = 0: transitions need the kept map", fn);
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(stats) % 8) return fail(ACCEL_ERR_ARG, "%s: stats = %p, device words must be 8-byte aligned", fn, stats);
+        if (reinterpret_cast<uintptr_t>(trans) % 8) return fail(ACCEL_ERR_ARG, "%s: trans = %p, device words must be 8-byte aligned", fn, trans);
+        if (reinterpret_cast<uintptr_t>(box) % 4) return fail(ACCEL_ERR_ARG, "%s: box = %p, device words must be 4-byte aligned", fn, box);
+    }
+    return 0;
+}
+
+// the summary of n maps in device memory (checked arguments), tracked against the model's kept map if asked
+static int model_summary(accel_model* m, const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, int track,
+                         uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared)
+{
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    accel_model::KeptLabels& k = m->kept_labels;
+    bool cmp = false;
+    unsigned char* kept = nullptr;
+    if (track) {
+        cmp = k.n == n && k.h == h && k.w == w && k.ncls == ncls;       // (then the map is large enough: nothing is reallocated)
+        k.n = 0;      // (whatever happens below, the old map is gone)
+        if (int rc = k.mem.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+        kept = k.mem.ptr;
+    }
+    if (!cmp) trans = nullptr;
+    const unsigned char* prev = trans ? kept : nullptr;
+    if (dst_on_device) {
+        HIP_TRY(launch_labels_summary(labels, n, H, W, out_h, out_w, h, w, ncls, prev, (size_t)w, reinterpret_cast<unsigned long long*>(stats), box,
+                                      reinterpret_cast<unsigned long long*>(trans), kept, (size_t)w, st));
+    } else {
+        const SummaryStage ss(n, ncls, stats, box, trans);
+        if (int rc = m->stage_out.reserve(m->ctx->device, ss.bytes)) return rc;
+        if (int rc = summary_to_host(labels, n, H, W, out_h, out_w, h, w, ncls, prev, (size_t)w, m->stage_out.ptr, ss, stats, box, trans, kept, (size_t)w, st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (track) { k.n = n; k.h = h; k.w = w; k.ncls = ncls; }
+    *compared = cmp ? 1 : 0;
+    return 0;
+}
+
+extern "C" int accel_model_labels_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track, uint64_t* stats, int32_t* box,
+                                          uint64_t* trans, int dst_on_device, int* compared)
+{
+    const char* fn = "accel_model_labels_summary";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const unsigned char* labels = nullptr;
+    if (int rc = model_labels(fn, m, n, &labels)) return rc;
+    const int H = m->labels_h, W = m->labels_w;
+    if (int rc = summary_args(fn, n, H, W, out_h, out_w, h, w, ncls)) return rc;
+    if (int rc = model_summary_args(fn, track, stats, box, trans, dst_on_device, compared)) return rc;
+    return model_summary(m, labels, n, H, W, out_h, out_w, h, w, ncls, track, stats, box, trans, dst_on_device, compared);
+}
+
+extern "C" int accel_model_scores_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track, uint64_t* stats, int32_t* box,
+                                          uint64_t* trans, int dst_on_device, int* compared)
+{
+    const char* fn = "accel_model_scores_summary";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const float* scores = nullptr;
+    int sncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &sncls, &H, &W)) return rc;
+    if (int rc = scores_labels_args(fn, n, sncls, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (int rc = model_summary_args(fn, track, stats, box, trans, dst_on_device, compared)) return rc;
+    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+    unsigned char* lab = m->interp_labels.ptr;
+    HIP_TRY(launch_scores_labels(scores, n, sncls, H, W, out_h, out_w, h, w, lab, (size_t)w, m->ctx->stream));
+    return model_summary(m, lab, n, h, w, h, w, h, w, ncls, track, stats, box, trans, dst_on_device, compared);      // the scratch at the identity geometry
+}
+
+extern "C" int accel_model_labels_forget(accel_model* m)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "accel_model_labels_forget: m is NULL");
+    m->kept_labels.n = 0;      // (the memory stays for the next clip)
     return 0;
 }
 

@@ -114,6 +114,13 @@ struct accel_model {
         int n = 0, out_h = 0, out_w = 0, cell = 0;
     };
     FrameSig sig_cur, sig_kept;
+    // accel_model_labels_summary / _scores_summary with track = 1: the previous frame's labels at the source size (n x h x w uint8, tight rows,
+    // allocated on first use), with what they were made under (n = 0: none; accel_model_labels_forget)
+    struct KeptLabels {
+        DevScratch mem;
+        int n = 0, h = 0, w = 0, ncls = 0;
+    };
+    KeptLabels kept_labels;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;

@@ -222,6 +222,14 @@ hipError_t launch_scores_confidence(const float* scores, int n, int ncls, int H,
 // A null output is left out, at least one is given.  Device pointers; the kernel only reads `img` and `sig_key`
 hipError_t launch_frame_change(const float* img, const int* sig_key, int n, int H, int W, int out_h, int out_w, int cell, int level_q, int* sig_out,
                                unsigned* changed, unsigned long long* sad, unsigned char* mask, size_t mask_pitch, hipStream_t st);
+// summary of finished frames (labels_summary.hip): the label maps and geometry of launch_labels_source -> per frame and class k < ncls (<= 32)
+// stats = (area, sum_x, sum_y) uint64 and box = (x0, y0, x1, y1) int32 (inclusive; (w, h, -1, -1) for an empty class) of the source pixels with that
+// label and, against prev (n x h rows prev_pitch bytes apart: the previous frame at the source size), trans[p * ncls + c] uint64 = the pixels that went
+// from p to c; kept (rows kept_pitch apart; may be prev itself) receives the current map at the source size: utils/image.py labels_summary_host.  All
+// results are overwritten.  A null output is left out, at least one is given, trans only with prev.  Device pointers; the kernel only reads `labels`
+hipError_t launch_labels_summary(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, const unsigned char* prev,
+                                 size_t prev_pitch, unsigned long long* stats, int* box, unsigned long long* trans, unsigned char* kept, size_t kept_pitch,
+                                 hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

@@ -259,6 +259,10 @@ def main(argv=None):
                     help='with --finish-on-gpu and --nv12 or --yuv: the labels blended over the frame IN ITS OWN FORMAT on the GPU (what an '
                          'encoder or a compositor takes; honours --interpolate); --out writes overlay_<frame>.png, the GPU\'s BGR '
                          'conversion of those bytes')
+    ap.add_argument('--summary', action='store_true',
+                    help='with --finish-on-gpu: per frame, the three largest classes with their share of the frame and their box, and from the '
+                         'second frame of a clip on the label churn against the previous frame -- counted on the GPU at the source size, a few '
+                         'hundred bytes per frame instead of the label map.  With --interpolate the labels are those of the interpolated scores')
     ap.add_argument('--adaptive-key', dest='adaptive_key', type=float, default=None, metavar='SHARE',
                     help='content-adaptive key frames: a frame becomes a key frame when more than SHARE (0 .. 1) of its cells changed against '
                          'the last key frame, measured on the GPU where the frame is; --interval is then the LONGEST distance between key '
@@ -280,6 +284,8 @@ def main(argv=None):
         raise ValueError("--confidence needs --finish-on-gpu")
     if args.interpolate and not args.finish_on_gpu:
         raise ValueError("--interpolate needs --finish-on-gpu")
+    if args.summary and not args.finish_on_gpu:
+        raise ValueError("--summary needs --finish-on-gpu")
     if args.nv12 and args.yuv:
         raise ValueError("--nv12 and --yuv are mutually exclusive: the frames are fed in one format")
     if args.overlay_yuv and not (args.finish_on_gpu and (args.nv12 or args.yuv)):
@@ -383,6 +389,17 @@ def main(argv=None):
                 from PIL import Image
                 os.makedirs(args.out, exist_ok=True)
                 Image.fromarray(conf[0]).save(os.path.join(args.out, 'conf_' + os.path.basename(names[idx])))
+        if args.summary:          # after the clock: what is in the frame, where, and did it just change -- no label map crosses PCIe for it
+            handle = lg if args.interpolate else lab
+            if idx % interv == 0:
+                results.forget(handle)        # a new clip: its first frame is not compared with the last one of another scene
+            s = results.summary(handle, source, ncls=num_classes, track=True, interpolate=args.interpolate)
+            area = s.stats[0, :, 0].astype(np.int64)
+            top = [k for k in np.argsort(-area, kind='stable')[:3] if area[k] > 0]
+            line = ' '.join('{}:{:.3f}[{},{},{},{}]'.format(k, area[k] / float(source['h'] * source['w']), *s.box[0, k]) for k in top)
+            if s.trans is not None:
+                line += ' churn {:.3f}'.format(float(results.summary_churn(s.trans)[0]))
+            print('summary ' + line)
         if args.out:
             from PIL import Image
             from .dataset.cityscape import getpallete

@@ -115,6 +115,10 @@ def _declare(lib):
         "accel_frame_change": [vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, sz],
         "accel_model_frame_change": [vp, c.c_char_p, i, i, i, i, i, vp, vp, vp, sz, i, c.POINTER(c.c_int)],
         "accel_model_frame_keep": [vp],
+        "accel_labels_summary": [vp, vp, i, i, i, i, i, i, i, i, vp, sz, vp, vp, vp, vp, sz],
+        "accel_model_labels_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
+        "accel_model_scores_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
+        "accel_model_labels_forget": [vp],
         "accel_labels_overlay_yuv": [vp, vp, i, i, i, i, i, c.POINTER(YUVLayout), vp, i, vp, vp],
         "accel_model_labels_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
         "accel_model_scores_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
@@ -641,6 +645,31 @@ class Context(object):
                                        opt(mk), pitch))
         return s, c, d, mk
 
+    def labels_summary(self, labels, out_h, out_w, h, w, ncls, prev=None, prev_width=None, stats=True, box=True, trans=None, kept=False):
+        """accel_labels_summary: n x H x W label maps whose valid region is out_h x out_w -> (stats, box, trans, kept) at the source size h x w --
+        per frame and class (area, sum_x, sum_y) as n x ncls x 3 uint64, the inclusive box (x0, y0, x1, y1) as n x ncls x 4 int32, against `prev`
+        (the previous frame's labels at the source size: n x h x w, or n x h x pitch bytes with `prev_width` = w) the transitions as
+        n x (ncls * ncls) uint64, and the current map at the source size, n x h x w uint8 (utils.image.labels_summary_host).  stats / box / trans
+        are True or False (left out: None is returned in its place; trans defaults to whether there is a `prev`); kept True, False or an array of
+        n x h x pitch bytes to write the rows into"""
+        a, n, H, W, _ = _u8_maps(labels)
+        h, w, ncls = int(h), int(w), int(ncls)
+        p, pp = None, 0
+        if prev is not None:
+            p, pn, ph, pw, pp = _u8_maps(prev, prev_width, "prev")
+            if (pn, ph, pw) != (n, h, w):
+                raise ValueError("prev of %d x %d x %d for a result of %d x %d x %d" % (pn, ph, pw, n, h, w))
+        if trans is None:
+            trans = prev is not None
+        cells = max(ncls, 0)
+        s = np.zeros((n, cells, 3), np.uint64) if stats else None
+        b = np.zeros((n, cells, 4), np.int32) if box else None
+        t = np.zeros((n, cells * cells), np.uint64) if trans else None
+        k, kp = (None, 0) if kept is None or kept is False else _result_rows(None if kept is True else kept, n, h, w, 1)
+        opt = lambda v: None if v is None else _fp(v)
+        check(lib().accel_labels_summary(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), h, w, ncls, opt(p), pp, opt(s), opt(b), opt(t), opt(k), kp))
+        return s, b, t, k
+
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
         _, _, H, W = cur.shape
@@ -1071,6 +1100,48 @@ class Model(object):
     def frame_keep(self):
         """accel_model_frame_keep: the current signature (the last frame_change) becomes the kept one, the one later frames are compared with"""
         check(lib().accel_model_frame_keep(self.handle))
+
+    # ---- summary of finished frames: it only READS `labels` / `logits` ------------------------------------------------------------
+    def _summary(self, fn, n, out_h, out_w, h, w, ncls, track, stats, box):
+        n, ncls = int(n), int(ncls)
+        cells = max(ncls, 0)
+        s = np.zeros((n, cells, 3), np.uint64) if stats else None
+        b = np.zeros((n, cells, 4), np.int32) if box else None
+        t = np.zeros((n, cells * cells), np.uint64) if track else None
+        compared = ctypes.c_int(0)
+        opt = lambda v: None if v is None else _fp(v)
+        check(fn(self.handle, n, int(out_h), int(out_w), int(h), int(w), ncls, int(bool(track)), opt(s), opt(b), opt(t), 0, ctypes.byref(compared)))
+        return s, b, t if compared.value else None
+
+    def _summary_device(self, fn, n, out_h, out_w, h, w, ncls, track, stats_ptr, box_ptr, trans_ptr):
+        vp = lambda v: ctypes.c_void_p(v) if v else None
+        compared = ctypes.c_int(0)
+        check(fn(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(ncls), int(bool(track)), vp(stats_ptr), vp(box_ptr), vp(trans_ptr), 1,
+                 ctypes.byref(compared)))
+        return bool(compared.value)
+
+    def labels_summary(self, n, out_h, out_w, h, w, ncls, track=False, stats=True, box=True):
+        """accel_model_labels_summary: (stats, box, trans) of the first n maps of `labels` at the source size h x w, as numpy arrays (see
+        Context.labels_summary).  track=True compares with the model's KEPT map -- trans is None where there was none made under the same
+        (n, h, w, ncls) -- and the current map becomes the kept one; track=False neither reads nor writes it.  It only READS `labels`"""
+        return self._summary(lib().accel_model_labels_summary, n, out_h, out_w, h, w, ncls, track, stats, box)
+
+    def labels_summary_device(self, n, out_h, out_w, h, w, ncls, track=False, stats_ptr=None, box_ptr=None, trans_ptr=None):
+        """the same into caller-owned HBM (enqueued, no host wait): n x ncls x 3 uint64, n x ncls x 4 int32, n x ncls x ncls uint64; -> whether
+        the kept map was compared with (trans is written only then)"""
+        return self._summary_device(lib().accel_model_labels_summary, n, out_h, out_w, h, w, ncls, track, stats_ptr, box_ptr, trans_ptr)
+
+    def scores_summary(self, n, out_h, out_w, h, w, ncls, track=False, stats=True, box=True):
+        """accel_model_scores_summary: labels_summary with the labels of the interpolated scores; the same kept map"""
+        return self._summary(lib().accel_model_scores_summary, n, out_h, out_w, h, w, ncls, track, stats, box)
+
+    def scores_summary_device(self, n, out_h, out_w, h, w, ncls, track=False, stats_ptr=None, box_ptr=None, trans_ptr=None):
+        """the same into caller-owned HBM (enqueued, no host wait)"""
+        return self._summary_device(lib().accel_model_scores_summary, n, out_h, out_w, h, w, ncls, track, stats_ptr, box_ptr, trans_ptr)
+
+    def labels_forget(self):
+        """accel_model_labels_forget: drop the kept map (a new clip, a cut): the next tracked summary compares with nothing"""
+        check(lib().accel_model_labels_forget(self.handle))
 
     # ---- labels from interpolated scores: they only READ `logits` ------------------------------------------------------------
     def scores_labels(self, n, out_h, out_w, h, w, out=None):

@@ -851,3 +851,76 @@ def frame_change_host(sig, sig_key, out_h, out_w, cell, level_q):
     d = np.abs(a - b)
     mask = d > level_q * frame_cell_areas(out_h, out_w, cell)[None]
     return mask.sum(axis=(1, 2)).astype(np.uint32), d.sum(axis=(1, 2)).astype(np.uint64), mask.astype(np.uint8)
+
+
+# ---- summary of finished frames: areas, coordinate sums, boxes and class transitions (csrc/labels_summary.hip restates it bit for bit) --------
+def labels_summary_host(labels, out_h, out_w, h, w, ncls, prev=None):
+    """The specification of accel_labels_summary.  `labels` is [n x] H x W uint8 with the valid region out_h x out_w; with
+        L(f, y, x) = labels[f][min(y * out_h // h, out_h - 1)][min(x * out_w // w, out_w - 1)]       (labels_to_source_host)
+    it returns (stats, box, trans, kept) for every frame f and class k in 0 .. ncls - 1 (ncls in 1 .. 32; ids >= ncls are ignored):
+        stats  n x ncls x 3 uint64: (area, sum_x, sum_y) over the source pixels (y, x) with L == k
+        box    n x ncls x 4 int32: (x0, y0, x1, y1), their inclusive extremes; (w, h, -1, -1) for a class without a pixel
+        trans  n x (ncls * ncls) uint64, or None without `prev` (n x h x w uint8, the previous frame's labels at the source size):
+               trans[f, p * ncls + c] = the source pixels with prev == p < ncls and L == c < ncls (rows: the previous frame)
+        kept   n x h x w uint8: the current map at the source size (labels_to_source_host), the `prev` of the next frame"""
+    a = np.asarray(labels, np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("labels must be [n x] H x W uint8, got shape %s" % (a.shape,))
+    n, H, W = a.shape
+    out_h, out_w, h, w, ncls = int(out_h), int(out_w), int(h), int(w), int(ncls)
+    if not (1 <= out_h <= H and 1 <= out_w <= W):
+        raise ValueError("out_h x out_w = %d x %d, must be in 1 x 1 .. H x W = %d x %d" % (out_h, out_w, H, W))
+    if not (1 <= h <= 32768 and 1 <= w <= 32768):
+        raise ValueError("h x w = %d x %d, must be in 1 .. 32768" % (h, w))
+    if not 1 <= ncls <= 32:
+        raise ValueError("ncls = %d, must be in 1 .. 32" % ncls)
+    kept = labels_to_source_host(a, out_h, out_w, h, w)
+    stats = np.zeros((n, ncls, 3), np.uint64)
+    box = np.empty((n, ncls, 4), np.int32)
+    box[...] = (w, h, -1, -1)
+    xs, ys = np.arange(w, dtype=np.uint64), np.arange(h, dtype=np.uint64)
+    for f in range(n):
+        for k in range(ncls):
+            mask = kept[f] == k
+            cols, rows = mask.sum(axis=0, dtype=np.uint64), mask.sum(axis=1, dtype=np.uint64)       # pixels of the class per column / per row
+            area = int(cols.sum())
+            if not area:
+                continue
+            stats[f, k] = (area, int((cols * xs).sum()), int((rows * ys).sum()))
+            cx, cy = np.nonzero(cols)[0], np.nonzero(rows)[0]
+            box[f, k] = (cx[0], cy[0], cx[-1], cy[-1])
+    trans = None
+    if prev is not None:
+        p = np.asarray(prev, np.uint8)
+        if p.ndim == 2:
+            p = p[None]
+        if p.shape != kept.shape:
+            raise ValueError("prev of shape %s for a source-size map of shape %s" % (p.shape, kept.shape))
+        trans = np.zeros((n, ncls * ncls), np.uint64)
+        for f in range(n):
+            ok = (p[f] < ncls) & (kept[f] < ncls)
+            pair = p[f][ok].astype(np.int64) * ncls + kept[f][ok].astype(np.int64)
+            trans[f] = np.bincount(pair, minlength=ncls * ncls).astype(np.uint64)
+    return stats, box, trans, kept
+
+
+def summary_centroids(stats):
+    """(sum_x / area, sum_y / area) of labels_summary_host's stats: float64 [...] x ncls x 2, NaN where the class is empty"""
+    s = np.asarray(stats).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(s[..., :1] > 0, s[..., 1:3] / s[..., :1], np.nan)
+
+
+def summary_churn(trans):
+    """the label churn per frame: 1 - trace / total of labels_summary_host's trans ([n x] ncls * ncls counts, one flat matrix per frame), the
+    share of counted pixels whose class changed; NaN where nothing was counted"""
+    t = np.asarray(trans).astype(np.float64)
+    ncls = int(round(t.shape[-1] ** 0.5))
+    if ncls * ncls != t.shape[-1]:
+        raise ValueError("trans must hold ncls * ncls counts per frame, got shape %s" % (t.shape,))
+    total = t.sum(axis=-1)
+    trace = t[..., ::ncls + 1].sum(axis=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(total > 0, 1.0 - trace / total, np.nan)

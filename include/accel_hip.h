@@ -504,6 +504,55 @@ int accel_model_frame_change(accel_model* m, const char* buf, int n, int out_h, 
                              uint8_t* mask, size_t mask_pitch, int dst_on_device, int* compared);
 int accel_model_frame_keep(accel_model* m);
 
+/* ---- finished frames: per-class areas, boxes, centroids and label churn -------------------------------------------------
+ * What is in a finished frame, where, and did it just change -- with no ground truth and no label map crossing PCIe: a few
+ * hundred bytes per frame (csrc/labels_summary.hip).  The geometry vocabulary is that of the finished-frames block: `labels`
+ * is n x H x W uint8, its valid region out_h x out_w, the source frame h x w, and source pixel (y, x) has the label
+ *   L(f, y, x) = labels[f][min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)]
+ * For every frame f and class k in 0 .. ncls - 1 (ncls in 1 .. 32; ids >= ncls are ignored, as the confusion matrix ignores
+ * them), integers throughout:
+ *   stats    n x ncls x 3 uint64      (area, sum_x, sum_y) over the source pixels with L == k; a sum reaches 2^15 * 2^30.  The
+ *                                     centroid is (sum_x / area, sum_y / area)
+ *   box      n x ncls x 4 int32       (x0, y0, x1, y1), the INCLUSIVE extremes of those pixels in source coordinates; a class
+ *                                     with no pixel has (w, h, -1, -1), the identities of min and max
+ *   trans    n x ncls x ncls uint64   against `prev`, the previous frame's labels AT THE SOURCE SIZE (n x h x w, frame i with
+ *                                     frame i): trans[f][p * ncls + c] = the source pixels with prev == p < ncls and L == c < ncls
+ *                                     (rows the previous frame, columns the current one).  Its off-diagonal share is the label
+ *                                     churn; the IoU per class of it is the temporal IoU
+ *   kept     n x h x w uint8          the current map at the source size: what accel_labels_to_source writes, and the `prev` of
+ *                                     the next frame.  Rows `kept_pitch` bytes apart; bytes between rows are not written
+ * All of them are OVERWRITTEN; being integer sums, minima and maxima they are exact and independent of the order of arrival.
+ * A NULL output is left out; at least one of stats / box / trans is given (or kept_out, at operator level).  One pass over
+ * the source pixels computes all of them; nothing outside out_h x out_w of `labels` is read.  The specification is
+ * accel_amd/utils/image.py labels_summary_host and the kernel equals it bit for bit.
+ * Argument errors (a NULL input, a size < 1 or > 32768, out_h > H, out_w > W, ncls outside 1 .. 32, a pitch smaller than a
+ * row, all outputs NULL, trans without prev -- at model level: with track = 0 --, n larger than the bound batch, no `labels`
+ * / `logits` buffer) return ACCEL_ERR_ARG before anything is enqueued, with a message that names the argument.
+ *   accel_labels_summary          operator level: host bytes in, host results out (the parity tests)
+ *   accel_model_labels_summary    on the model's `labels` buffer (H, W as the bound plans write it), enqueued on the context
+ *                                 stream after the run that wrote it.  It only reads `labels`: no write generation changes, no
+ *                                 captured graph is touched.  track = 1 compares with the model-owned KEPT map (n x h x w,
+ *                                 allocated on first use, freed with the model) if that was made under the same (n, h, w,
+ *                                 ncls): *compared is then 1 and trans is written; otherwise *compared is 0 and trans is not
+ *                                 written.  Either way the current map becomes the kept one, in the same pass.  track = 0
+ *                                 neither reads nor writes the kept map (*compared = 0).  Host destinations (dst_on_device =
+ *                                 0) are filled when the call returns, device destinations (= 1: all of them, stats and trans
+ *                                 8-byte and box 4-byte aligned) when the stream reaches them
+ *   accel_model_scores_summary    the same of the labels of the bilinearly INTERPOLATED scores (accel_model_scores_labels):
+ *                                 they are written into the model's n x h x w scratch and summarised at the identity geometry.
+ *                                 `ncls` is the summary's class count, 1 .. 32; the class count of the scores is that of
+ *                                 `logits`.  It only reads `logits`.  One kept map serves both forms
+ *   accel_model_labels_forget     drops the kept map (a new clip, a cut): the next tracked call compares with nothing.  Not an
+ *                                 error when there is none */
+int accel_labels_summary(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls,
+                         const uint8_t* prev /* NULL, or n x h x w */, size_t prev_pitch,
+                         uint64_t* stats, int32_t* box, uint64_t* trans, uint8_t* kept_out /* NULL, or n x h x w */, size_t kept_pitch);
+int accel_model_labels_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track,
+                               uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared);
+int accel_model_scores_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track,
+                               uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared);
+int accel_model_labels_forget(accel_model* m);
+
 /* ---- finished frames: the overlay in the frame's own format ------------------------------------------------------------
  * The label map blended over NV12, I420 / YV12, P010 or YUY2 frames and written as the same format in the same layout
  * (csrc/overlay_yuv.hip): what an encoder, a compositor or a capture-card output takes, with no BGR picture in between.
