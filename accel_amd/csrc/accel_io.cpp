@@ -174,8 +174,8 @@ struct DevTemps {
     void* upload(const void* host, size_t bytes) { void* p = get(bytes); if (p && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
 };
 
-// ---- uint8 frames ---------------------------------------------------------------------------------------------------------------
-// The resize a frame conversion is told (out_h, out_w, step) and the padded size H x W, for an h x w source: shared by the BGR and the NV12 route.
+// ---- frames in: what the BGR route and the YUV routes share --------------------------------------------------------------------------------
+// The resize a frame conversion is told (out_h, out_w, step) and the padded size H x W, for an h x w source.
 static int frame_resize_args(const char* fn, int h, int w, int out_h, int out_w, double step, int H, int W)
 {
     if (!(step > 0.0) || step > 1e9) return fail(ACCEL_ERR_ARG, "%s: step = %g, must be a positive number of source pixels per output pixel", fn, step);
@@ -185,19 +185,6 @@ static int frame_resize_args(const char* fn, int h, int w, int out_h, int out_w,
     if (step == 1.0 && (out_h != h || out_w != w))
         return fail(ACCEL_ERR_ARG, "%s: step = 1 copies the frame, but out_h x out_w = %d x %d is not h x w = %d x %d", fn, out_h, out_w, h, w);
     return 0;
-}
-
-// Geometry of a uint8 frame conversion, checked before anything is enqueued: every message names the argument at fault.
-static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
-                         int H, int W)
-{
-    if (!bgr) return fail(ACCEL_ERR_ARG, "%s: bgr is NULL", fn);
-    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
-    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
-    if (h < 1) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be >= 1", fn, h);
-    if (w < 1) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be >= 1", fn, w);
-    if (pitch < (size_t)3 * w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %zu", fn, pitch, w, (size_t)3 * w);
-    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
 }
 
 static int frame_u8_buf(const char* fn, accel_model* m, const char* buf, int n, int H, int W, DevBuf** out)
@@ -211,26 +198,49 @@ static int frame_u8_buf(const char* fn, accel_model* m, const char* buf, int n, 
     return 0;
 }
 
-extern "C" int accel_frame_u8(accel_ctx* ctx, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
-                              int out_h, int out_w, double step, int H, int W, float* out)
+// Host frames of `src_bytes` bytes, converted by `launch(src, dst, stream)` into n x 3 x H x W fp32 of host memory: the operator-level entry points
+template <class Launch>
+static int frames_to_host(const char* fn, accel_ctx* ctx, const void* src, size_t src_bytes, int n, int H, int W, float* out, Launch launch)
 {
-    const char* fn = "accel_frame_u8";
-    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_u8: NULL argument");
-    if (int rc = frame_u8_args(fn, bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t ob = (size_t)n * 3 * H * W * 4;
     DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(bgr, (size_t)n * h * pitch));
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(src, src_bytes));
     float* d = static_cast<float*>(t.get(ob));
     if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    HIP_TRY(launch_frames_u8(s, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
+    HIP_TRY(launch(s, d, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
     return 0;
 }
 
-// Frames of `src_bytes` bytes, converted by `launch(src, dst, stream)` into the image input `buf` of n x 3 x H x W fp32: what the BGR and the NV12
-// route share once their own arguments are checked.  A host source goes through the staging buffer.
+// n frames of h x w pixels as BGR bytes, by `launch(src, dst, dst_pitch, stream)`.  on_device: enqueued from `src` into `bgr_out`, and that is
+// all.  Host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are.
+template <class Launch>
+static int bgr_rows(const char* fn, accel_ctx* ctx, const uint8_t* src, size_t src_bytes, int n, int h, int w, uint8_t* bgr_out, size_t out_pitch,
+                    int on_device, Launch launch)
+{
+    const size_t row = (size_t)3 * w;
+    if (!bgr_out) return fail(ACCEL_ERR_ARG, "%s: bgr_out is NULL", fn);
+    if (out_pitch < row || out_pitch > ((size_t)1 << 40))
+        return fail(ACCEL_ERR_ARG, "%s: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", fn, out_pitch, w, row);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (on_device) {
+        HIP_TRY(launch(src, bgr_out, out_pitch, ctx->stream));
+        return 0;
+    }
+    DevTemps t;
+    const unsigned char* s = static_cast<const unsigned char*>(t.upload(src, src_bytes));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * row));
+    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch(s, d, row, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, row, row, (size_t)n * h, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Frames of `src_bytes` bytes, converted by `launch(src, dst, stream)` into the image input `buf` of n x 3 x H x W fp32, once their own arguments
+// are checked.  A host source goes through the staging buffer.
 template <class Launch>
 static int write_frames(const char* fn, accel_model* m, const char* buf, int n, int H, int W, const unsigned char* src, size_t src_bytes,
                         int src_on_device, Launch launch)
@@ -242,6 +252,48 @@ static int write_frames(const char* fn, accel_model* m, const char* buf, int n, 
     HIP_TRY(launch(src, static_cast<float*>(b->ptr), m->ctx->stream));
     m->source_written(buf);
     return 0;
+}
+
+// The bytes that accel_model_prefetch_u8 put into the uint8 shadow of `buf` (bytes are bytes: BGR, NV12, P010's words), converted by
+// `launch(src, dst, stream)` into the image input.  `check(dev, &need)` is the family's own argument check: it is told the address the kernel
+// will read (P010's alignment needs it) and says how many bytes the frames occupy; `formula` is how the family words that size.
+template <class Check, class Launch>
+static int commit_frames(const char* fn, accel_model* m, const char* buf, int n, int H, int W, const char* formula, Check check, Launch launch)
+{
+    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "%s: unknown buffer '%s'", fn, buf);
+    Shadow* sh = prefetched(m->shadows_u8, buf);
+    if (!sh) return fail(ACCEL_ERR_ARG, "%s: no uint8 frames were prefetched for '%s'", fn, buf);
+    size_t need = 0;
+    if (int rc = check(sh->mem.ptr, &need)) return rc;
+    DevBuf* b = nullptr;
+    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
+    if (need > sh->filled) return fail(ACCEL_ERR_ARG, "%s: %s = %zu bytes, %zu were prefetched for '%s'", fn, formula, need, sh->filled, buf);
+    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) { return launch(src, static_cast<float*>(dst), st); });
+}
+
+// ---- BGR frames (frames_u8.hip) ------------------------------------------------------------------------------------------------------------
+// Geometry of a uint8 frame conversion, checked before anything is enqueued: every message names the argument at fault.
+static int frame_u8_args(const char* fn, const void* bgr, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
+                         int H, int W)
+{
+    if (!bgr) return fail(ACCEL_ERR_ARG, "%s: bgr is NULL", fn);
+    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
+    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
+    if (h < 1) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be >= 1", fn, h);
+    if (w < 1) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be >= 1", fn, w);
+    if (pitch < (size_t)3 * w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %zu", fn, pitch, w, (size_t)3 * w);
+    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
+}
+
+extern "C" int accel_frame_u8(accel_ctx* ctx, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
+                              int out_h, int out_w, double step, int H, int W, float* out)
+{
+    const char* fn = "accel_frame_u8";
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_u8: NULL argument");
+    if (int rc = frame_u8_args(fn, bgr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return frames_to_host(fn, ctx, bgr, (size_t)n * h * pitch, n, H, W, out, [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, dst, st);
+    });
 }
 
 extern "C" int accel_model_write_u8(accel_model* m, const char* buf, const uint8_t* bgr, int n, int h, int w, size_t pitch, const double* means_bgr,
@@ -268,20 +320,15 @@ extern "C" int accel_model_commit_u8(accel_model* m, const char* buf, int n, int
 {
     const char* fn = "accel_model_commit_u8";
     if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: NULL argument");
-    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: unknown buffer '%s'", buf);
-    Shadow* sh = prefetched(m->shadows_u8, buf);
-    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: no uint8 frames were prefetched for '%s'", buf);
-    if (int rc = frame_u8_args(fn, sh->mem.ptr, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W)) return rc;
-    DevBuf* b = nullptr;
-    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
-    if ((size_t)n * h * pitch > sh->filled)
-        return fail(ACCEL_ERR_ARG, "accel_model_commit_u8: n x h x pitch = %d x %d x %zu bytes, %zu were prefetched for '%s'", n, h, pitch, sh->filled, buf);
-    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
-        return launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
+    return commit_frames(fn, m, buf, n, H, W, "n x h x pitch", [&](const void* dev, size_t* need) {
+        *need = (size_t)n * h * pitch;
+        return frame_u8_args(fn, dev, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W);
+    }, [&](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_u8(src, n, h, w, pitch, means_bgr, out_h, out_w, step, H, W, dst, st);
     });
 }
 
-// ---- NV12 frames (frames_nv12.hip) ------------------------------------------------------------------------------------------------
+// ---- YUV frames: I420, P010, YUY2 and NV12, replicated or sited chroma (frames_yuv.h; frames_yuv.hip, frames_sited.hip) --------------------
 extern "C" int accel_nv12_coefficients(int colour, int32_t out[6])
 {
     if (!out) return fail(ACCEL_ERR_ARG, "accel_nv12_coefficients: out is NULL");
@@ -291,118 +338,6 @@ extern "C" int accel_nv12_coefficients(int colour, int32_t out[6])
     return 0;
 }
 
-// Layout of NV12 frames, checked before anything is enqueued: every message names the argument at fault.
-static int nv12_layout_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour)
-{
-    const int lim = 32768;
-    if (!nv12) return fail(ACCEL_ERR_ARG, "%s: nv12 is NULL", fn);
-    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
-    if (h < 2 || h > lim || h % 2) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be even and in 2 .. %d", fn, h, lim);
-    if (w < 2 || w > lim || w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 2 .. %d", fn, w, lim);
-    if (pitch < (size_t)w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d pixels has %d", fn, pitch, w, w);
-    if (pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, pitch);
-    if (uv_offset < (size_t)h * pitch)
-        return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, uv_offset, h, pitch, (size_t)h * pitch);
-    if (uv_offset > ((size_t)1 << 60)) return fail(ACCEL_ERR_ARG, "%s: uv_offset = %zu bytes is not an offset into a frame", fn, uv_offset);
-    if (frame_bytes < uv_offset + (size_t)(h / 2) * pitch)
-        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the chroma plane at uv_offset = %zu ends at %zu", fn, frame_bytes, uv_offset,
-                    uv_offset + (size_t)(h / 2) * pitch);
-    if (frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, frame_bytes);
-    if (colour < 0 || colour > 3) return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, colour);
-    return 0;
-}
-
-static int frame_nv12_args(const char* fn, const void* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                           const double* means_bgr, int out_h, int out_w, double step, int H, int W)
-{
-    if (int rc = nv12_layout_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
-    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
-    return frame_resize_args(fn, h, w, out_h, out_w, step, H, W);
-}
-
-// the bytes n frames occupy: the last one ends with its chroma plane
-static size_t nv12_bytes(int n, int h, size_t pitch, size_t uv_offset, size_t frame_bytes)
-{
-    return (size_t)(n - 1) * frame_bytes + uv_offset + (size_t)(h / 2) * pitch;
-}
-
-extern "C" int accel_frame_nv12(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                                const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* out)
-{
-    const char* fn = "accel_frame_nv12";
-    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_nv12: NULL argument");
-    if (int rc = frame_nv12_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t ob = (size_t)n * 3 * H * W * 4;
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes)));
-    float* d = static_cast<float*>(t.get(ob));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    HIP_TRY(launch_frames_nv12(s, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int accel_nv12_to_bgr(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                                 uint8_t* bgr_out, size_t out_pitch, int on_device)
-{
-    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: NULL argument");
-    if (int rc = nv12_layout_args("accel_nv12_to_bgr", nv12, n, h, w, pitch, uv_offset, frame_bytes, colour)) return rc;
-    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: bgr_out is NULL");
-    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
-        return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (on_device) {
-        HIP_TRY(launch_nv12_to_bgr(nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, bgr_out, out_pitch, ctx->stream));
-        return 0;
-    }
-    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes)));
-    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_nv12_to_bgr: device allocation or upload failed");
-    HIP_TRY(launch_nv12_to_bgr(s, n, h, w, pitch, uv_offset, frame_bytes, colour, d, (size_t)3 * w, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset,
-                                      size_t frame_bytes, int colour, const double* means_bgr, int out_h, int out_w, double step, int H, int W,
-                                      int src_on_device)
-{
-    const char* fn = "accel_model_write_nv12";
-    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_nv12: NULL argument");
-    if (int rc = frame_nv12_args(fn, nv12, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
-    return write_frames(fn, m, buf, n, H, W, nv12, nv12_bytes(n, h, pitch, uv_offset, frame_bytes), src_on_device,
-                        [&](const unsigned char* src, float* dst, hipStream_t st) {
-        return launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, dst, st);
-    });
-}
-
-// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow: bytes are bytes)
-extern "C" int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                                       const double* means_bgr, int out_h, int out_w, double step, int H, int W)
-{
-    const char* fn = "accel_model_commit_nv12";
-    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: NULL argument");
-    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: unknown buffer '%s'", buf);
-    Shadow* sh = prefetched(m->shadows_u8, buf);
-    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: no uint8 frames were prefetched for '%s'", buf);
-    if (int rc = frame_nv12_args(fn, sh->mem.ptr, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W)) return rc;
-    DevBuf* b = nullptr;
-    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
-    const size_t need = nv12_bytes(n, h, pitch, uv_offset, frame_bytes);
-    if (need > sh->filled)
-        return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: (n - 1) x frame_bytes + uv_offset + h/2 x pitch = %zu bytes, %zu were prefetched for '%s'",
-                    need, sh->filled, buf);
-    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
-        return launch_frames_nv12(src, n, h, w, pitch, uv_offset, frame_bytes, colour, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
-    });
-}
-
-// ---- I420, P010 and YUY2 frames (frames_yuv.hip) ----------------------------------------------------------------------------------
 extern "C" int accel_yuv10_coefficients(int colour, int32_t out[6])
 {
     if (!out) return fail(ACCEL_ERR_ARG, "accel_yuv10_coefficients: out is NULL");
@@ -412,42 +347,69 @@ extern "C" int accel_yuv10_coefficients(int colour, int32_t out[6])
     return 0;
 }
 
-enum { YUV_I420 = 0, YUV_P010 = 1, YUV_YUY2 = 2 };
+enum { YUV_I420 = 0, YUV_P010 = 1, YUV_YUY2 = 2, YUV_NV12 = 3 };
 
 // the bytes one frame occupies: one past the last byte of the last row of its last plane (planes of I420 may interleave, so no whole pitch is
-// counted for the last row)
+// counted for the last row; the last chroma row of format 3 ends after w bytes)
 static size_t yuv_extent(const accel_yuv_layout& y)
 {
     const size_t h = (size_t)y.h, w = (size_t)y.w;
     if (y.format == YUV_I420) return (y.u_offset > y.v_offset ? y.u_offset : y.v_offset) + (h / 2 - 1) * y.pitch_c + w / 2;
     if (y.format == YUV_P010) return y.u_offset + (h / 2 - 1) * y.pitch + 2 * w;
+    if (y.format == YUV_NV12) return y.u_offset + (h / 2 - 1) * y.pitch + w;
     return (h - 1) * y.pitch + 2 * w;
 }
 
-// the bytes n frames occupy: the last one ends with its extent
-static size_t yuv_bytes(int n, const accel_yuv_layout& y)
+// the same for the accel_*_nv12 entry points, which ask for a whole pitch of the last chroma row (include/accel_hip.h)
+static size_t nv12_extent(const accel_yuv_layout& y)
 {
-    return (size_t)(n - 1) * y.frame_bytes + yuv_extent(y);
+    return y.u_offset + (size_t)(y.h / 2) * y.pitch;
 }
 
-// Layout of I420 / P010 / YUY2 frames, checked before anything is enqueued: every message names the argument at fault.  `dev`: the address the
-// kernel will read if the caller's pointer is device memory, else NULL (host bytes are uploaded into an aligned buffer).
-static int yuv_layout_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, const void* dev)
+// What tells the families of entry points apart when a layout is checked: what their signatures call the frames and the chroma offset, the
+// highest format they take, and where a frame ends.
+struct LayoutRules { const char* src; const char* chroma; int max_format; size_t (*extent)(const accel_yuv_layout&); };
+static const LayoutRules NV12_ARGS = {"nv12", "uv_offset", YUV_NV12, nv12_extent};      // accel_*_nv12: the layout is made of their scalars
+static const LayoutRules YUV_ARGS = {"yuv", "u_offset", YUV_YUY2, yuv_extent};          // accel_*_yuv
+static const LayoutRules SITED_ARGS = {"yuv", "u_offset", YUV_NV12, yuv_extent};        // accel_*_yuv_sited, and the overlay
+
+static accel_yuv_layout nv12_layout(int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour)
+{
+    return {YUV_NV12, colour, h, w, pitch, 0, uv_offset, 0, frame_bytes};
+}
+
+static YuvLayout kernel_layout(const accel_yuv_layout& y)
+{
+    return {y.format, y.colour, y.h, y.w, y.pitch, y.pitch_c, y.u_offset, y.v_offset, y.frame_bytes};
+}
+
+// the bytes n frames occupy: the last one ends with its extent
+static size_t frames_bytes(int n, const accel_yuv_layout& y, const LayoutRules& r)
+{
+    return (size_t)(n - 1) * y.frame_bytes + r.extent(y);
+}
+
+// Layout and siting of YUV frames, checked before anything is enqueued: every message names the argument at fault, as the caller's signature
+// names it.  `dev`: the address the kernel will read if the caller's pointer is device memory, else NULL (host bytes are uploaded into an aligned
+// buffer).
+static int yuv_layout_args(const char* fn, const LayoutRules& r, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev)
 {
     const int lim = 32768;
-    static const char* const names[3] = {"I420", "P010", "YUY2"};
-    if (!yuv) return fail(ACCEL_ERR_ARG, "%s: yuv is NULL", fn);
+    static const char* const names[4] = {"I420", "P010", "YUY2", "NV12"};
+    if (!yuv) return fail(ACCEL_ERR_ARG, "%s: %s is NULL", fn, r.src);
     if (!lay) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
+    if (siting < 0 || siting > 3) return fail(ACCEL_ERR_ARG, "%s: siting = %d, must be 0 (replicate), 1 (left), 2 (centre) or 3 (topleft)", fn, siting);
     const accel_yuv_layout& y = *lay;
     if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
-    if (y.format < 0 || y.format > 2) return fail(ACCEL_ERR_ARG, "%s: format = %d, must be 0 (I420), 1 (P010) or 2 (YUY2)", fn, y.format);
+    if (y.format < 0 || y.format > r.max_format)
+        return fail(ACCEL_ERR_ARG, "%s: format = %d, must be 0 (I420), 1 (P010)%s", fn, y.format, r.max_format == YUV_NV12 ? ", 2 (YUY2) or 3 (NV12)" : " or 2 (YUY2)");
     const char* name = names[y.format];
     if (y.colour < 0 || y.colour > 3)
         return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, y.colour);
-    const bool even_h = y.format != YUV_YUY2;
+    const bool even_h = y.format != YUV_YUY2, words = y.format == YUV_P010 || y.format == YUV_YUY2;
     if (y.h < 1 || y.h > lim || (even_h && y.h % 2)) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be %sin 1 .. %d for %s", fn, y.h, even_h ? "even and " : "", lim, name);
     if (y.w < 1 || y.w > lim || y.w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 1 .. %d for %s", fn, y.w, lim, name);
-    const size_t row = y.format == YUV_I420 ? (size_t)y.w : (size_t)2 * y.w;
+    const size_t row = words ? (size_t)2 * y.w : (size_t)y.w;
     if (y.pitch < row) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d %s pixels has %zu", fn, y.pitch, y.w, name, row);
     if (y.pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, y.pitch);
     const size_t luma_end = (size_t)y.h * y.pitch;
@@ -460,32 +422,87 @@ static int yuv_layout_args(const char* fn, const void* yuv, int n, const accel_y
         if (y.format == YUV_YUY2 && y.u_offset) return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu, but YUY2 has no such field: it must be 0", fn, y.u_offset);
     }
     if (y.format != YUV_YUY2 && (y.u_offset < luma_end || y.u_offset > ((size_t)1 << 60)))
-        return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.u_offset, y.h, y.pitch, luma_end);
+        return fail(ACCEL_ERR_ARG, "%s: %s = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, r.chroma, y.u_offset, y.h, y.pitch, luma_end);
     if (y.format == YUV_I420 && (y.v_offset < luma_end || y.v_offset > ((size_t)1 << 60)))
         return fail(ACCEL_ERR_ARG, "%s: v_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.v_offset, y.h, y.pitch, luma_end);
-    if (y.frame_bytes < yuv_extent(y))
-        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the last plane of a frame ends at %zu", fn, y.frame_bytes, yuv_extent(y));
+    if (y.frame_bytes < r.extent(y))
+        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the last plane of a frame ends at %zu", fn, y.frame_bytes, r.extent(y));
     if (y.frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, y.frame_bytes);
     if (y.format == YUV_P010) {       // every 16-bit word is read as one
         if (y.pitch % 2) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu, P010 words are 2-byte aligned: it must be even", fn, y.pitch);
         if (y.u_offset % 2) return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu, P010 words are 2-byte aligned: it must be even", fn, y.u_offset);
         if (y.frame_bytes % 2) return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, P010 words are 2-byte aligned: it must be even", fn, y.frame_bytes);
-        if (reinterpret_cast<uintptr_t>(dev) % 2) return fail(ACCEL_ERR_ARG, "%s: yuv = %p, P010 words are 2-byte aligned: a device address must be even", fn, dev);
+        if (reinterpret_cast<uintptr_t>(dev) % 2) return fail(ACCEL_ERR_ARG, "%s: %s = %p, P010 words are 2-byte aligned: a device address must be even", fn, r.src, dev);
     }
     return 0;
 }
 
-static int frame_yuv_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, const void* dev, const double* means_bgr, int out_h,
-                          int out_w, double step, int H, int W)
+static int frame_yuv_args(const char* fn, const LayoutRules& r, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev,
+                          const double* means_bgr, int out_h, int out_w, double step, int H, int W)
 {
-    if (int rc = yuv_layout_args(fn, yuv, n, lay, dev)) return rc;
+    if (int rc = yuv_layout_args(fn, r, yuv, n, lay, siting, dev)) return rc;
     if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
     return frame_resize_args(fn, lay->h, lay->w, out_h, out_w, step, H, W);
 }
 
-static YuvLayout kernel_layout(const accel_yuv_layout& y)
+// the `launch(src, dst, stream)` of the YUV routes into the image tensor (`lay` is read at the launch: after the checks)
+static auto frames_yuv_launch(int n, const accel_yuv_layout* lay, int siting, const double* means_bgr, int out_h, int out_w, double step, int H, int W)
 {
-    return {y.format, y.colour, y.h, y.w, y.pitch, y.pitch_c, y.u_offset, y.v_offset, y.frame_bytes};
+    return [=](const unsigned char* src, float* dst, hipStream_t st) {
+        return launch_frames_yuv(src, n, kernel_layout(*lay), siting, means_bgr, out_h, out_w, step, H, W, dst, st);
+    };
+}
+
+// and their `launch(src, dst, dst_pitch, stream)` into BGR bytes
+static auto yuv_to_bgr_launch(int n, const accel_yuv_layout* lay, int siting)
+{
+    return [=](const unsigned char* src, unsigned char* dst, size_t dst_pitch, hipStream_t st) {
+        return launch_yuv_to_bgr(src, n, kernel_layout(*lay), siting, dst, dst_pitch, st);
+    };
+}
+
+extern "C" int accel_frame_nv12(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* out)
+{
+    const char* fn = "accel_frame_nv12";
+    const accel_yuv_layout lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes, colour);
+    if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_nv12: NULL argument");
+    if (int rc = frame_yuv_args(fn, NV12_ARGS, nv12, n, &lay, 0, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return frames_to_host(fn, ctx, nv12, frames_bytes(n, lay, NV12_ARGS), n, H, W, out, frames_yuv_launch(n, &lay, 0, means_bgr, out_h, out_w, step, H, W));
+}
+
+extern "C" int accel_nv12_to_bgr(accel_ctx* ctx, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                 uint8_t* bgr_out, size_t out_pitch, int on_device)
+{
+    const char* fn = "accel_nv12_to_bgr";
+    const accel_yuv_layout lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes, colour);
+    if (!ctx) return fail(ACCEL_ERR_ARG, "accel_nv12_to_bgr: NULL argument");
+    if (int rc = yuv_layout_args(fn, NV12_ARGS, nv12, n, &lay, 0, nullptr)) return rc;
+    return bgr_rows(fn, ctx, nv12, frames_bytes(n, lay, NV12_ARGS), n, h, w, bgr_out, out_pitch, on_device, yuv_to_bgr_launch(n, &lay, 0));
+}
+
+extern "C" int accel_model_write_nv12(accel_model* m, const char* buf, const uint8_t* nv12, int n, int h, int w, size_t pitch, size_t uv_offset,
+                                      size_t frame_bytes, int colour, const double* means_bgr, int out_h, int out_w, double step, int H, int W,
+                                      int src_on_device)
+{
+    const char* fn = "accel_model_write_nv12";
+    const accel_yuv_layout lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes, colour);
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_nv12: NULL argument");
+    if (int rc = frame_yuv_args(fn, NV12_ARGS, nv12, n, &lay, 0, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return write_frames(fn, m, buf, n, H, W, nv12, frames_bytes(n, lay, NV12_ARGS), src_on_device,
+                        frames_yuv_launch(n, &lay, 0, means_bgr, out_h, out_w, step, H, W));
+}
+
+extern "C" int accel_model_commit_nv12(accel_model* m, const char* buf, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
+                                       const double* means_bgr, int out_h, int out_w, double step, int H, int W)
+{
+    const char* fn = "accel_model_commit_nv12";
+    const accel_yuv_layout lay = nv12_layout(h, w, pitch, uv_offset, frame_bytes, colour);
+    if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_nv12: NULL argument");
+    return commit_frames(fn, m, buf, n, H, W, "(n - 1) x frame_bytes + uv_offset + h/2 x pitch", [&](const void* dev, size_t* need) {
+        *need = frames_bytes(n, lay, NV12_ARGS);
+        return frame_yuv_args(fn, NV12_ARGS, dev, n, &lay, 0, dev, means_bgr, out_h, out_w, step, H, W);
+    }, frames_yuv_launch(n, &lay, 0, means_bgr, out_h, out_w, step, H, W));
 }
 
 extern "C" int accel_frame_yuv(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h, int out_w,
@@ -493,41 +510,16 @@ extern "C" int accel_frame_yuv(accel_ctx* ctx, const uint8_t* yuv, int n, const 
 {
     const char* fn = "accel_frame_yuv";
     if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_yuv: NULL argument");
-    if (int rc = frame_yuv_args(fn, yuv, n, layout, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t ob = (size_t)n * 3 * H * W * 4;
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, yuv_bytes(n, *layout)));
-    float* d = static_cast<float*>(t.get(ob));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    HIP_TRY(launch_frames_yuv(s, n, kernel_layout(*layout), means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
-    return 0;
+    if (int rc = frame_yuv_args(fn, YUV_ARGS, yuv, n, layout, 0, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return frames_to_host(fn, ctx, yuv, frames_bytes(n, *layout, YUV_ARGS), n, H, W, out, frames_yuv_launch(n, layout, 0, means_bgr, out_h, out_w, step, H, W));
 }
 
 extern "C" int accel_yuv_to_bgr(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch, int on_device)
 {
+    const char* fn = "accel_yuv_to_bgr";
     if (!ctx) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: NULL argument");
-    if (int rc = yuv_layout_args("accel_yuv_to_bgr", yuv, n, layout, on_device ? yuv : nullptr)) return rc;
-    const int h = layout->h, w = layout->w;
-    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: bgr_out is NULL");
-    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
-        return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (on_device) {
-        HIP_TRY(launch_yuv_to_bgr(yuv, n, kernel_layout(*layout), bgr_out, out_pitch, ctx->stream));
-        return 0;
-    }
-    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, yuv_bytes(n, *layout)));
-    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_yuv_to_bgr: device allocation or upload failed");
-    HIP_TRY(launch_yuv_to_bgr(s, n, kernel_layout(*layout), d, (size_t)3 * w, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
-    return 0;
+    if (int rc = yuv_layout_args(fn, YUV_ARGS, yuv, n, layout, 0, on_device ? yuv : nullptr)) return rc;
+    return bgr_rows(fn, ctx, yuv, frames_bytes(n, *layout, YUV_ARGS), n, layout->h, layout->w, bgr_out, out_pitch, on_device, yuv_to_bgr_launch(n, layout, 0));
 }
 
 extern "C" int accel_model_write_yuv(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr,
@@ -535,127 +527,42 @@ extern "C" int accel_model_write_yuv(accel_model* m, const char* buf, const uint
 {
     const char* fn = "accel_model_write_yuv";
     if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_yuv: NULL argument");
-    if (int rc = frame_yuv_args(fn, yuv, n, layout, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    const YuvLayout y = kernel_layout(*layout);
-    return write_frames(fn, m, buf, n, H, W, yuv, yuv_bytes(n, *layout), src_on_device, [&](const unsigned char* src, float* dst, hipStream_t st) {
-        return launch_frames_yuv(src, n, y, means_bgr, out_h, out_w, step, H, W, dst, st);
-    });
+    if (int rc = frame_yuv_args(fn, YUV_ARGS, yuv, n, layout, 0, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return write_frames(fn, m, buf, n, H, W, yuv, frames_bytes(n, *layout, YUV_ARGS), src_on_device,
+                        frames_yuv_launch(n, layout, 0, means_bgr, out_h, out_w, step, H, W));
 }
 
-// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow: bytes are bytes, P010's words among them)
 extern "C" int accel_model_commit_yuv(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
                                       int out_w, double step, int H, int W)
 {
     const char* fn = "accel_model_commit_yuv";
     if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: NULL argument");
-    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: unknown buffer '%s'", buf);
-    Shadow* sh = prefetched(m->shadows_u8, buf);
-    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: no uint8 frames were prefetched for '%s'", buf);
-    if (int rc = frame_yuv_args(fn, sh->mem.ptr, n, layout, sh->mem.ptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    DevBuf* b = nullptr;
-    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
-    const size_t need = yuv_bytes(n, *layout);
-    if (need > sh->filled)
-        return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv: (n - 1) x frame_bytes + the extent of a frame = %zu bytes, %zu were prefetched for '%s'",
-                    need, sh->filled, buf);
-    const YuvLayout y = kernel_layout(*layout);
-    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
-        return launch_frames_yuv(src, n, y, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
-    });
+    return commit_frames(fn, m, buf, n, H, W, "(n - 1) x frame_bytes + the extent of a frame", [&](const void* dev, size_t* need) {
+        if (int rc = frame_yuv_args(fn, YUV_ARGS, dev, n, layout, 0, dev, means_bgr, out_h, out_w, step, H, W)) return rc;
+        *need = frames_bytes(n, *layout, YUV_ARGS);
+        return 0;
+    }, frames_yuv_launch(n, layout, 0, means_bgr, out_h, out_w, step, H, W));
 }
 
-// ---- the same frames, and NV12 as format 3, with interpolated chroma siting (frames_sited.hip) -------------------------------------------
-enum { YUV_NV12 = 3 };
-
-// one past the last byte of a frame, format 3 included: its last chroma row ends after w bytes
-static size_t sited_extent(const accel_yuv_layout& y)
-{
-    if (y.format == YUV_NV12) return y.u_offset + ((size_t)y.h / 2 - 1) * y.pitch + (size_t)y.w;
-    return yuv_extent(y);
-}
-
-static size_t sited_bytes(int n, const accel_yuv_layout& y)
-{
-    return (size_t)(n - 1) * y.frame_bytes + sited_extent(y);
-}
-
-// Layout and siting, checked before anything is enqueued: what yuv_layout_args asks of formats 0 .. 2, NV12's fields of format 3, siting 0 .. 3.
-static int yuv_sited_layout_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev)
-{
-    const int lim = 32768;
-    if (!yuv) return fail(ACCEL_ERR_ARG, "%s: yuv is NULL", fn);
-    if (!lay) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
-    if (siting < 0 || siting > 3) return fail(ACCEL_ERR_ARG, "%s: siting = %d, must be 0 (replicate), 1 (left), 2 (centre) or 3 (topleft)", fn, siting);
-    const accel_yuv_layout& y = *lay;
-    if (y.format < 0 || y.format > 3) return fail(ACCEL_ERR_ARG, "%s: format = %d, must be 0 (I420), 1 (P010), 2 (YUY2) or 3 (NV12)", fn, y.format);
-    if (y.format != YUV_NV12) return yuv_layout_args(fn, yuv, n, lay, dev);
-    if (n < 1) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be >= 1", fn, n);
-    if (y.colour < 0 || y.colour > 3)
-        return fail(ACCEL_ERR_ARG, "%s: colour = %d, must be in 0 .. 3 (BT.601 limited / full, BT.709 limited / full)", fn, y.colour);
-    if (y.h < 2 || y.h > lim || y.h % 2) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be even and in 2 .. %d for NV12", fn, y.h, lim);
-    if (y.w < 2 || y.w > lim || y.w % 2) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be even and in 2 .. %d for NV12", fn, y.w, lim);
-    if (y.pitch < (size_t)y.w) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes, a row of w = %d NV12 pixels has %d", fn, y.pitch, y.w, y.w);
-    if (y.pitch > ((size_t)1 << 40)) return fail(ACCEL_ERR_ARG, "%s: pitch = %zu bytes is not a row pitch", fn, y.pitch);
-    if (y.pitch_c) return fail(ACCEL_ERR_ARG, "%s: pitch_c = %zu, but NV12 has no such field: it must be 0", fn, y.pitch_c);
-    if (y.v_offset) return fail(ACCEL_ERR_ARG, "%s: v_offset = %zu, but NV12 has no such field: it must be 0", fn, y.v_offset);
-    const size_t luma_end = (size_t)y.h * y.pitch;
-    if (y.u_offset < luma_end || y.u_offset > ((size_t)1 << 60))
-        return fail(ACCEL_ERR_ARG, "%s: u_offset = %zu bytes, the luma plane of h x pitch = %d x %zu ends at %zu", fn, y.u_offset, y.h, y.pitch, luma_end);
-    if (y.frame_bytes < sited_extent(y))
-        return fail(ACCEL_ERR_ARG, "%s: frame_bytes = %zu, the last plane of a frame ends at %zu", fn, y.frame_bytes, sited_extent(y));
-    if (y.frame_bytes > ((size_t)1 << 61) / (size_t)n) return fail(ACCEL_ERR_ARG, "%s: n x frame_bytes = %d x %zu bytes is not a buffer size", fn, n, y.frame_bytes);
-    return 0;
-}
-
-static int frame_yuv_sited_args(const char* fn, const void* yuv, int n, const accel_yuv_layout* lay, int siting, const void* dev,
-                                const double* means_bgr, int out_h, int out_w, double step, int H, int W)
-{
-    if (int rc = yuv_sited_layout_args(fn, yuv, n, lay, siting, dev)) return rc;
-    if (!means_bgr) return fail(ACCEL_ERR_ARG, "%s: means_bgr is NULL", fn);
-    return frame_resize_args(fn, lay->h, lay->w, out_h, out_w, step, H, W);
-}
-
+// the same frames, and NV12 as format 3, with the chroma siting the caller names
 extern "C" int accel_frame_yuv_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
                                      int out_w, double step, int H, int W, float* out, int siting)
 {
     const char* fn = "accel_frame_yuv_sited";
     if (!ctx || !out) return fail(ACCEL_ERR_ARG, "accel_frame_yuv_sited: NULL argument");
-    if (int rc = frame_yuv_sited_args(fn, yuv, n, layout, siting, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t ob = (size_t)n * 3 * H * W * 4;
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, sited_bytes(n, *layout)));
-    float* d = static_cast<float*>(t.get(ob));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    HIP_TRY(launch_frames_yuv_sited(s, n, kernel_layout(*layout), siting, means_bgr, out_h, out_w, step, H, W, d, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(out, d, ob, hipMemcpyDeviceToHost));
-    return 0;
+    if (int rc = frame_yuv_args(fn, SITED_ARGS, yuv, n, layout, siting, nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return frames_to_host(fn, ctx, yuv, frames_bytes(n, *layout, SITED_ARGS), n, H, W, out,
+                          frames_yuv_launch(n, layout, siting, means_bgr, out_h, out_w, step, H, W));
 }
 
 extern "C" int accel_yuv_to_bgr_sited(accel_ctx* ctx, const uint8_t* yuv, int n, const accel_yuv_layout* layout, uint8_t* bgr_out, size_t out_pitch,
                                       int siting, int on_device)
 {
+    const char* fn = "accel_yuv_to_bgr_sited";
     if (!ctx) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: NULL argument");
-    if (int rc = yuv_sited_layout_args("accel_yuv_to_bgr_sited", yuv, n, layout, siting, on_device ? yuv : nullptr)) return rc;
-    const int h = layout->h, w = layout->w;
-    if (!bgr_out) return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: bgr_out is NULL");
-    if (out_pitch < (size_t)3 * w || out_pitch > ((size_t)1 << 40))
-        return fail(ACCEL_ERR_ARG, "accel_yuv_to_bgr_sited: out_pitch = %zu bytes, a row of w = %d BGR pixels has %zu", out_pitch, w, (size_t)3 * w);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (on_device) {
-        HIP_TRY(launch_yuv_to_bgr_sited(yuv, n, kernel_layout(*layout), siting, bgr_out, out_pitch, ctx->stream));
-        return 0;
-    }
-    // host in, host out: the rows of the result are written `out_pitch` apart, the bytes between them are left as they are
-    DevTemps t;
-    const unsigned char* s = static_cast<const unsigned char*>(t.upload(yuv, sited_bytes(n, *layout)));
-    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * (size_t)3 * w));
-    if (!s || !d) return fail(ACCEL_ERR_HIP, "accel_yuv_to_bgr_sited: device allocation or upload failed");
-    HIP_TRY(launch_yuv_to_bgr_sited(s, n, kernel_layout(*layout), siting, d, (size_t)3 * w, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy2D(bgr_out, out_pitch, d, (size_t)3 * w, (size_t)3 * w, (size_t)n * h, hipMemcpyDeviceToHost));
-    return 0;
+    if (int rc = yuv_layout_args(fn, SITED_ARGS, yuv, n, layout, siting, on_device ? yuv : nullptr)) return rc;
+    return bgr_rows(fn, ctx, yuv, frames_bytes(n, *layout, SITED_ARGS), n, layout->h, layout->w, bgr_out, out_pitch, on_device,
+                    yuv_to_bgr_launch(n, layout, siting));
 }
 
 extern "C" int accel_model_write_yuv_sited(accel_model* m, const char* buf, const uint8_t* yuv, int n, const accel_yuv_layout* layout,
@@ -663,33 +570,21 @@ extern "C" int accel_model_write_yuv_sited(accel_model* m, const char* buf, cons
 {
     const char* fn = "accel_model_write_yuv_sited";
     if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_write_yuv_sited: NULL argument");
-    if (int rc = frame_yuv_sited_args(fn, yuv, n, layout, siting, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    const YuvLayout y = kernel_layout(*layout);
-    return write_frames(fn, m, buf, n, H, W, yuv, sited_bytes(n, *layout), src_on_device, [&](const unsigned char* src, float* dst, hipStream_t st) {
-        return launch_frames_yuv_sited(src, n, y, siting, means_bgr, out_h, out_w, step, H, W, dst, st);
-    });
+    if (int rc = frame_yuv_args(fn, SITED_ARGS, yuv, n, layout, siting, src_on_device ? yuv : nullptr, means_bgr, out_h, out_w, step, H, W)) return rc;
+    return write_frames(fn, m, buf, n, H, W, yuv, frames_bytes(n, *layout, SITED_ARGS), src_on_device,
+                        frames_yuv_launch(n, layout, siting, means_bgr, out_h, out_w, step, H, W));
 }
 
-// (the bytes were prefetched with accel_model_prefetch_u8 into the uint8 shadow, as for accel_model_commit_yuv)
 extern "C" int accel_model_commit_yuv_sited(accel_model* m, const char* buf, int n, const accel_yuv_layout* layout, const double* means_bgr, int out_h,
                                             int out_w, double step, int H, int W, int siting)
 {
     const char* fn = "accel_model_commit_yuv_sited";
     if (!m || !buf) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: NULL argument");
-    if (!m->pbufs.count(buf)) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: unknown buffer '%s'", buf);
-    Shadow* sh = prefetched(m->shadows_u8, buf);
-    if (!sh) return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: no uint8 frames were prefetched for '%s'", buf);
-    if (int rc = frame_yuv_sited_args(fn, sh->mem.ptr, n, layout, siting, sh->mem.ptr, means_bgr, out_h, out_w, step, H, W)) return rc;
-    DevBuf* b = nullptr;
-    if (int rc = frame_u8_buf(fn, m, buf, n, H, W, &b)) return rc;
-    const size_t need = sited_bytes(n, *layout);
-    if (need > sh->filled)
-        return fail(ACCEL_ERR_ARG, "accel_model_commit_yuv_sited: (n - 1) x frame_bytes + the extent of a frame = %zu bytes, %zu were prefetched for '%s'",
-                    need, sh->filled, buf);
-    const YuvLayout y = kernel_layout(*layout);
-    return commit_from(m, buf, *b, *sh, [&](const unsigned char* src, void* dst, hipStream_t st) {
-        return launch_frames_yuv_sited(src, n, y, siting, means_bgr, out_h, out_w, step, H, W, static_cast<float*>(dst), st);
-    });
+    return commit_frames(fn, m, buf, n, H, W, "(n - 1) x frame_bytes + the extent of a frame", [&](const void* dev, size_t* need) {
+        if (int rc = frame_yuv_args(fn, SITED_ARGS, dev, n, layout, siting, dev, means_bgr, out_h, out_w, step, H, W)) return rc;
+        *need = frames_bytes(n, *layout, SITED_ARGS);
+        return 0;
+    }, frames_yuv_launch(n, layout, siting, means_bgr, out_h, out_w, step, H, W));
 }
 
 // ---- finished frames: labels at the source size, confusion matrix, colour image (results_u8.hip) ---------------------------------------
@@ -1197,7 +1092,7 @@ static int overlay_args(const char* fn, int n, const accel_yuv_layout* layout, c
     if (!layout) return fail(ACCEL_ERR_ARG, "%s: layout is NULL", fn);
     *lay = *layout;
     lay->colour = 0;
-    if (int rc = yuv_sited_layout_args(fn, frame, n, lay, 0, nullptr)) return rc;
+    if (int rc = yuv_layout_args(fn, SITED_ARGS, frame, n, lay, 0, nullptr)) return rc;
     if (lay->format == YUV_P010 && reinterpret_cast<uintptr_t>(frame_dev) % 2)
         return fail(ACCEL_ERR_ARG, "%s: frame = %p, P010 words are 2-byte aligned: a device address must be even", fn, frame_dev);
     if (lay->format == YUV_P010 && reinterpret_cast<uintptr_t>(dst_dev) % 2)
@@ -1229,7 +1124,7 @@ extern "C" int accel_labels_overlay_yuv(accel_ctx* ctx, const uint8_t* labels, i
     HIP_TRY(hipSetDevice(ctx->device));
     // host in, host out: the destination starts as a copy of the frame, so the bytes that are not samples are the input's
     DevTemps t;
-    const size_t bytes = sited_bytes(n, lay);
+    const size_t bytes = frames_bytes(n, lay, SITED_ARGS);
     const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
     const unsigned char* s = static_cast<const unsigned char*>(t.upload(frame, bytes));
     unsigned char* d = static_cast<unsigned char*>(t.upload(frame, bytes));
@@ -1249,7 +1144,7 @@ static int overlay_frames(accel_model* m, int n, const accel_yuv_layout& lay, co
 {
     hipStream_t st = m->ctx->stream;
     const YuvLayout y = kernel_layout(lay);
-    const size_t bytes = sited_bytes(n, lay);
+    const size_t bytes = frames_bytes(n, lay, SITED_ARGS);
     HIP_TRY(hipSetDevice(m->ctx->device));
     if (dst_on_device) {
         const unsigned char* f = frame;

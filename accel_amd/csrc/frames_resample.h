@@ -1,4 +1,4 @@
-// The float64 arithmetic of accel_amd/utils/image.py that the frame kernels (frames_u8.hip, frames_nv12.hip) restate bit for bit: where the four
+// The float64 arithmetic of accel_amd/utils/image.py that the frame kernels (frames_u8.hip, frames_yuv.h) restate bit for bit: where the four
 // taps of _resize_bilinear lie, how they are blended, and how a grey level becomes the centred fp32 value.  Every operation is an IEEE double
 // operation rounded on its own (hipcc contracts a*b + c into an fma in device code by default; numpy does not).
 #pragma once

@@ -20,7 +20,7 @@ using frames::Means;
 using frames::centred;
 
 // One grey level of the resized image: _resize_bilinear of utils/image.py for channel c of output pixel (x, y), whose taps are `t`
-// (frames_resample.h holds the arithmetic, shared with frames_nv12.hip).
+// (frames_resample.h holds the arithmetic, shared with frames_yuv.h).
 __device__ __forceinline__ int resample(const unsigned char* __restrict__ img, size_t pitch, const frames::Taps& t, int c)
 {
     const unsigned char* r0 = img + (size_t)t.y0 * pitch + c;

@@ -152,32 +152,19 @@ hipError_t launch_set_slot(const void** slot, const void* value, hipStream_t st)
 // bytes themselves, out_h == h and out_w == w), mean removed in float64, padding = fp32(-mean); bit for bit utils/image.py
 hipError_t launch_frames_u8(const unsigned char* src, int n, int h, int w, size_t pitch, const double* means_bgr, int out_h, int out_w, double step,
                             int H, int W, float* dst, hipStream_t st);
-// NV12 frames (frames_nv12.hip): n frames in device memory, each h rows of w luma bytes `pitch` apart from byte 0 and, at byte `uv_offset`, h / 2
-// rows of w / 2 (Cb, Cr) pairs at the same pitch, `frame_bytes` from frame to frame (h, w even) -> the tensor launch_frames_u8 writes for the BGR
-// frames image.nv12_to_bgr_host makes of them (`colour` 0 .. 3: BT.601 / BT.709, limited / full range; integer arithmetic, replicated chroma),
-// bit for bit -- and those BGR bytes themselves, rows `out_pitch` apart.  nv12_coefficients: the six integers of a colour mode, or nullptr.
-const int32_t* nv12_coefficients(int colour);
-hipError_t launch_frames_nv12(const unsigned char* src, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                              const double* means_bgr, int out_h, int out_w, double step, int H, int W, float* dst, hipStream_t st);
-hipError_t launch_nv12_to_bgr(const unsigned char* src, int n, int h, int w, size_t pitch, size_t uv_offset, size_t frame_bytes, int colour,
-                              unsigned char* dst, size_t out_pitch, hipStream_t st);
-// I420, P010 and YUY2 frames (frames_yuv.hip): n frames in device memory laid out as `y` says (the fields of accel_yuv_layout, include/accel_hip.h:
-// format 0 I420, 1 P010, 2 YUY2; a field a format does not use is 0) -> the tensor launch_frames_u8 writes for the BGR frames
-// image.yuv_to_bgr_host makes of them, bit for bit -- and those BGR bytes themselves, rows `out_pitch` apart.  The 8-bit formats convert with
-// nv12_coefficients; yuv10_coefficients: the six integers of a colour mode for P010's 10-bit samples, or nullptr.
+// I420, P010, YUY2 and NV12 frames (frames_yuv.h; frames_yuv.hip, frames_sited.hip): n frames in device memory laid out as `y` says (the fields of
+// accel_yuv_layout, include/accel_hip.h: format 0 I420, 1 P010, 2 YUY2, 3 NV12 -- interleaved 8-bit chroma at `u_offset`, rows `pitch` apart; a
+// field a format does not use is 0) -> the tensor launch_frames_u8 writes for the BGR frames image.yuv_to_bgr_host(siting = s) makes of them
+// (image.nv12_to_bgr_host for format 3), bit for bit -- and those BGR bytes themselves, rows `out_pitch` apart.  `colour` 0 .. 3: BT.601 / BT.709,
+// limited / full range, in integer arithmetic.  `siting` 0: replicated chroma; 1 left, 2 centre, 3 topleft: Cb and Cr are interpolated to the
+// luma pixel by the integer rule of image.chroma_upsample before the colour rule.  nv12_coefficients: the six integers of a colour mode for the
+// 8-bit formats, yuv10_coefficients: for P010's 10-bit samples; or nullptr.
 struct YuvLayout { int format, colour, h, w; size_t pitch, pitch_c, u_offset, v_offset, frame_bytes; };
+const int32_t* nv12_coefficients(int colour);
 const int32_t* yuv10_coefficients(int colour);
-hipError_t launch_frames_yuv(const unsigned char* src, int n, const YuvLayout& y, const double* means_bgr, int out_h, int out_w, double step,
-                             int H, int W, float* dst, hipStream_t st);
-hipError_t launch_yuv_to_bgr(const unsigned char* src, int n, const YuvLayout& y, unsigned char* dst, size_t out_pitch, hipStream_t st);
-// The same with interpolated chroma siting (frames_sited.hip): `siting` 1 left, 2 centre, 3 topleft -- Cb and Cr are interpolated to the luma
-// pixel by the integer rule of image.chroma_upsample before the colour rule -- the tensor and the bytes of image.yuv_to_bgr_host(siting = s),
-// bit for bit.  Format 3 is NV12 here: interleaved 8-bit chroma at `u_offset`, rows `pitch` apart (image.nv12_to_bgr_host).  Siting 0 calls the
-// launchers above, and those of NV12 for format 3.
-hipError_t launch_frames_yuv_sited(const unsigned char* src, int n, const YuvLayout& y, int siting, const double* means_bgr, int out_h, int out_w,
-                                   double step, int H, int W, float* dst, hipStream_t st);
-hipError_t launch_yuv_to_bgr_sited(const unsigned char* src, int n, const YuvLayout& y, int siting, unsigned char* dst, size_t out_pitch,
-                                   hipStream_t st);
+hipError_t launch_frames_yuv(const unsigned char* src, int n, const YuvLayout& y, int siting, const double* means_bgr, int out_h, int out_w,
+                             double step, int H, int W, float* dst, hipStream_t st);
+hipError_t launch_yuv_to_bgr(const unsigned char* src, int n, const YuvLayout& y, int siting, unsigned char* dst, size_t out_pitch, hipStream_t st);
 // finished frames (results_u8.hip): n label maps of H x W bytes (valid region out_h x out_w, top left) taken to the source size h x w by the
 // integer nearest rule labels[min(y * out_h / h, out_h - 1)][min(x * out_w / w, out_w - 1)] -- as labels (rows `dst_pitch` apart), as counts added
 // to an ncls x ncls matrix of 64-bit words (rows gt, columns prediction, ids >= ncls ignored; ncls <= 32), or as n x h x w x 3 colours
@@ -190,7 +177,7 @@ hipError_t launch_labels_hist(const unsigned char* labels, int n, int H, int W, 
 hipError_t launch_labels_colour(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, const unsigned char* palette_rgb,
                                 int rgb_order, const unsigned char* frame, size_t frame_pitch, int alpha, unsigned char* dst, size_t dst_pitch, hipStream_t st);
 // the overlay in the frame's own format (overlay_yuv.hip): the same label maps and geometry, h x w = y.h x y.w, blended with weight alpha / 256
-// over n frames laid out as `y` says (formats 0 .. 2 as above, 3 = NV12 as for the sited launchers; y.colour is not looked at) into `dst`, which
+// over n frames laid out as `y` says (formats 0 .. 3 as above; y.colour is not looked at) into `dst`, which
 // has the same layout and may be `frame` itself (otherwise disjoint from it).  palette_ycc: 768 host words, (Y, Cb, Cr) per label in the units of
 // the samples (utils/image.py palette_ycbcr).  Integer arithmetic, one rounding per sample: utils/image.py overlay_yuv_host, bit for bit.  Bytes
 // that are not samples are neither read nor written.  labels, frame and dst are device memory; the kernel only reads `labels`

@@ -11,20 +11,15 @@
 // One rounding per sample and no clip: a convex combination stays inside the range of its operands.  uint32 throughout (<= 256 * 4 * 1023 + 512).
 // The overlay's chroma is the block mean of the palette colours whatever the siting of the frame's samples, which are blended where they are.
 //
-// A thread owns the 4-pixel x ROWS patch of frames_yuv.hip -- whole 2 x 2 (YUY2: 1 x 2) blocks -- reads all its samples, then stores them: no
+// A thread owns the 4-pixel x ROWS patch of frames_yuv.h -- whole 2 x 2 (YUY2: 1 x 2) blocks -- reads all its samples, then stores them: no
 // thread reads a sample another writes, so dst == frame (in place on a decoder's surface) is allowed and the two pointers carry no __restrict__.
 // Bytes that are not samples (between rows, between planes, after a frame) are neither read nor written.
 // A bandwidth kernel: about 1 label byte + the frame's bytes in, the frame's bytes out.
-#include "kernels.h"
-#include <stdint.h>
+#include "frames_yuv.h"
 
 namespace {
 
-enum { I420 = 0, P010 = 1, YUY2 = 2, NV12 = 3 };
-
-struct Layout { size_t pitch, pitch_c, u_offset, v_offset, frame_bytes; };
-
-template <int F> struct Patch { static constexpr int ROWS = F == YUY2 ? 1 : 2; };
+using namespace yuv;      // the formats, Layout, Patch, word10
 
 struct TableYcc { uint16_t ycc[768]; };       // passed BY VALUE: 1536 bytes of kernel argument, no allocation, ordered with the stream for free
 
@@ -52,7 +47,6 @@ __device__ __forceinline__ int source_row(int y, int out_h, int h)
     return min((int)((unsigned)y * (unsigned)out_h / (unsigned)h), out_h - 1);
 }
 
-__device__ __forceinline__ unsigned word10(const unsigned char* p) { return *reinterpret_cast<const uint16_t*>(p) >> 6; }
 __device__ __forceinline__ void store10(unsigned char* p, unsigned v) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)(v << 6); }
 
 // WIDE: the layout, the source and the destination address allow the wide accesses of a whole patch (wide_access below) --

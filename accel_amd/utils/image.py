@@ -387,7 +387,7 @@ def chroma_upsample(plane, h, w, siting, vertical=True):
 
 
 def yuv_to_bgr(y, cb, cr, colour=0):
-    """The integer rule, the specification of csrc/frames_nv12.hip: arrays of Y, Cb, Cr bytes -> (B, G, R) uint8 arrays.  With c = Y - yoff,
+    """The integer rule, the specification of csrc/frames_yuv.h: arrays of Y, Cb, Cr bytes -> (B, G, R) uint8 arrays.  With c = Y - yoff,
     d = Cb - 128, e = Cr - 128 in int32 and arithmetic right shifts: R = clip((ky c + krv e + 32768) >> 16), G = clip((ky c - kgu d - kgv e +
     32768) >> 16), B = clip((ky c + kbu d + 32768) >> 16)."""
     yoff, ky, krv, kgu, kgv, kbu = nv12_coefficients(colour)

@@ -203,7 +203,7 @@ int accel_model_commit_u8(accel_model* m, const char* buf, int n, int h, int w, 
 /* ---- NV12 video frames -------------------------------------------------------------------------------------------
  * What a hardware or software video decoder hands out: a full-size 8-bit luma plane followed by a half-height plane of
  * interleaved Cb, Cr at half resolution.  The bytes are uploaded as they are (1.5 per pixel) and one kernel
- * (csrc/frames_nv12.hip) converts the colour, resizes, removes the mean and pads: the tensor is, bit for bit,
+ * (csrc/frames_yuv.hip) converts the colour, resizes, removes the mean and pads: the tensor is, bit for bit,
  * transform(resize(nv12_to_bgr_host(frame))) of accel_amd/utils/image.py -- what the uint8 route above gives for the
  * BGR frames the conversion below makes.
  *   nv12, n, h, w         n frames; h and w are even, 2 .. 32768

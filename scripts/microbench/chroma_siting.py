@@ -1,5 +1,5 @@
-"""What interpolated chroma siting (csrc/frames_sited.hip) costs beside the replicated kernels of the same format (csrc/frames_nv12.hip,
-csrc/frames_yuv.hip), on frames resident in HBM:
+"""What interpolated chroma siting (csrc/frames_sited.hip) costs beside the replicated kernels of the same format
+(csrc/frames_yuv.hip), on frames resident in HBM:
 
     python scripts/microbench/chroma_siting.py [--size 1024x2048] [--source 720x1280] [--frames 1 8] [--train 200] [--rounds 5] [--repeats 3] [--out FILE]
 

@@ -1,4 +1,4 @@
-"""What NV12 frames cost and save against raw BGR frames (accel_model_prefetch_u8 / _commit_nv12, csrc/frames_nv12.hip): Accel-18, kf=5, at 1024x2048
+"""What NV12 frames cost and save against raw BGR frames (accel_model_prefetch_u8 / _commit_nv12, csrc/frames_yuv.hip): Accel-18, kf=5, at 1024x2048
 (step 1: the frame is copied) and 720x1280 (resampled to 1024x1820, padded to 1024x1824), one clip per call and 8 clips per call.
 
     python scripts/microbench/nv12.py [--sizes 1024x2048 720x1280] [--batches 1 8] [--seconds 1.0] [--repeats 3] [--out profiles/nv12.md]

@@ -1,4 +1,4 @@
-"""What the I420, P010 and YUY2 kernels (csrc/frames_yuv.hip) cost beside the NV12 kernels (csrc/frames_nv12.hip), on frames resident in HBM:
+"""What the I420, P010 and YUY2 kernels cost beside the NV12 kernels (all in csrc/frames_yuv.hip), on frames resident in HBM:
 
     python scripts/microbench/yuv.py [--size 1024x2048] [--source 720x1280] [--frames 1 8] [--train 200] [--rounds 5] [--repeats 3] [--out FILE]
 

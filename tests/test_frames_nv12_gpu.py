@@ -1,4 +1,4 @@
-"""NV12 video frames on the GPU (csrc/frames_nv12.hip behind accel_frame_nv12 / accel_nv12_to_bgr / accel_model_write_nv12 / _commit_nv12): the
+"""NV12 video frames on the GPU (csrc/frames_yuv.hip behind accel_frame_nv12 / accel_nv12_to_bgr / accel_model_write_nv12 / _commit_nv12): the
 tensor the kernel writes is the one accel_amd/utils/image.py builds on the host -- transform(resize(nv12_to_bgr_host(frame))) as fp32 -- BIT FOR
 BIT.  The colour conversion is integer arithmetic and what follows it is the float64 arithmetic of the uint8 route with one defined rounding, so
 every comparison is np.array_equal: no tolerance.  Random frames draw luma and both chroma bytes independently, so a wrong chroma row, column or
