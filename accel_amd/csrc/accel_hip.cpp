@@ -558,23 +558,24 @@ static int finalize_conv(accel_plan* p, Op& op)
     c.w = static_cast<const float*>(dw_);
     {
         // fp32 layers also get their weights as three bf16 planes: the bf16x3 kernel (conv_igemm.hip) is then one more
-        // launch geometry (70-74) of the SAME fp32 convolution for the autotuner (ACCEL_WITHHOLD=split withholds it)
-        const int ft = (int)kv_int(kv, "tile", -1);
-        const bool forced = (ft >= CONV_TILE_B3 && ft < CONV_TILE_B3D + CONV_TILE_B3D_N) || (ft >= 90 && ft <= 96);
+        // launch geometry (family b3) of the SAME fp32 convolution for the autotuner (ACCEL_WITHHOLD=split withholds it).  A forced id
+        // that reads one of these copies gets it made (asked of the table's row: the id is checked against this build further down)
+        const ConvTile* ft = conv_tile_row((int)kv_int(kv, "tile", -1));
+        const bool forced_r = ft && (ft->weights == CONV_W_WB3R || ft->weights == CONV_W_WH2R);
+        const bool forced = forced_r || (ft && ft->weights == CONV_W_WB3);
         if (!c.f16 && c.Cin % 4 == 0 && cout_store > 4 && (!withheld("split") || forced)) {
             std::vector<uint16_t> pb;
             pack_bf16x3(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, pb, c.w_plane);
             void* d3 = nullptr;
             if ((rc = dev_upload(p, pb.data(), pb.size() * sizeof(uint16_t), &d3))) return rc;
             c.wb3 = d3;
-            const bool forced_r = (ft >= CONV_TILE_B3R && ft < CONV_TILE_B3D + CONV_TILE_B3D_N) || (ft >= 90 && ft <= 96);
             if (!withheld("b3r") || forced_r) {      // the fragment-ordered copy for the second-generation kernel
                 pack_bf16x3r(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, pb, c.w_plane);
                 void* d4 = nullptr;
                 if ((rc = dev_upload(p, pb.data(), pb.size() * sizeof(uint16_t), &d4))) return rc;
                 c.wb3r = d4;
             }
-        } else if (forced && !(c.f16 == 1 && c.wb3r && ft >= CONV_TILE_B3R && ft < CONV_TILE_B3D + CONV_TILE_B3D_N)) {
+        } else if (forced && !(c.f16 == 1 && c.wb3r && forced_r && !(ft->flags & CONV_T_DIAG))) {
             return fail(ACCEL_ERR_ARG, "conv %s: the bf16x3 kernel takes layers with more than "
                                        "4 output channels only", op.name.c_str());
         }
@@ -690,10 +691,11 @@ static int finalize_conv(accel_plan* p, Op& op)
     c.force_tile = (int)kv_int(kv, "tile", -1);
     if (c.force_tile >= 0 && !conv_tile_valid(c.force_tile))
         return fail(ACCEL_ERR_ARG, "conv %s: launch geometry id %d is not part of this build", op.name.c_str(), c.force_tile);
+    const int forced_w = c.force_tile >= 0 ? conv_tile(c.force_tile)->weights : -1;      // the weight copy a forced id reads
     {
         // Winograd F(2x2,3x3) form of the layer (3x3 / stride 1 / dilation 1 / pad 1): weights transformed here, in
         // double, once; offered to the autotuner beside the direct tiles (ACCEL_WITHHOLD=winograd withholds it)
-        const bool want = !withheld("winograd") || c.force_tile == CONV_TILE_WINO;
+        const bool want = !withheld("winograd") || forced_w == CONV_W_WU;
         c.M = op.a.N * c.Ho * c.Wo;
         if (want && !cols && cin == cin_pad && conv_wino_eligible(c)) {
             c.wino_rows = conv_wino_rows(cout_store);
@@ -706,7 +708,7 @@ static int finalize_conv(accel_plan* p, Op& op)
             // accuracy budget: Winograd evaluations carry about 3x the rounding error of a direct one, and the plan decides which
             // layers may take the split form (conv key wb3=0 withholds it)
             const bool wb3_ok = kv_int(kv, "wb3", 1) != 0;
-            const bool wb3_forced = c.force_tile == CONV_TILE_WINO_B3 || c.force_tile == CONV_TILE_WINO_B3U || c.force_tile == CONV_TILE_WINO_B3S;
+            const bool wb3_forced = forced_w == CONV_W_WUB;
             if (((!withheld("split") && !withheld("winograd_split") && wb3_ok) || wb3_forced) && !c.f16 && conv_wino_b3_eligible(c)) {
                 // the same transformed weights as three exact bf16 planes in MFMA fragment order: launch geometry 41
                 std::vector<unsigned short> ub;
@@ -727,14 +729,14 @@ static int finalize_conv(accel_plan* p, Op& op)
                     c.scale_h2w = static_cast<const float*>(dsh);
                 }
             }
-        } else if (c.force_tile == CONV_TILE_WINO || c.force_tile == CONV_TILE_WINO_B3 || c.force_tile == CONV_TILE_WINO_B3U || c.force_tile == CONV_TILE_WINO_B3S) {
+        } else if (forced_w == CONV_W_WU || forced_w == CONV_W_WUB) {
             return fail(ACCEL_ERR_ARG, "conv %s: the Winograd kernel takes 3x3 / stride 1 / dilation 1 / pad 1 layers with even output "
                                        "size and channels in multiples of 8 only", op.name.c_str());
         }
     }
     {
         // direct stem kernel (7x7 / stride 2 / pad 3, 3-channel image, 64 output channels): per-lane weight arrangement
-        const bool want = !withheld("stem") || c.force_tile == CONV_TILE_STEM || c.force_tile == CONV_TILE_STEM_B3;
+        const bool want = !withheld("stem") || forced_w == CONV_W_WSTEM || forced_w == CONV_W_WSTEMB;
         c.Cout_store = cout_store;
         c.res = op.d.set ? op.d.ptr : nullptr;
         if (want && !cols && cin == 3 && cout == 64 && conv_stem_eligible(c)) {
@@ -743,7 +745,7 @@ static int finalize_conv(accel_plan* p, Op& op)
             void* dsw = nullptr;
             if ((rc = dev_upload(p, ws.data(), ws.size() * sizeof(float), &dsw))) return rc;
             c.wstem = static_cast<const float*>(dsw);
-            if ((!withheld("split") && !withheld("stem_split")) || c.force_tile == CONV_TILE_STEM_B3) {
+            if ((!withheld("split") && !withheld("stem_split")) || forced_w == CONV_W_WSTEMB) {
                 // the same layer for the bf16 matrix cores: three exact bf16 planes in MFMA fragment order (launch geometry 51)
                 std::vector<unsigned short> wb;
                 conv_stem_b3_pack(w->data.data(), cout, wb);
@@ -762,14 +764,14 @@ static int finalize_conv(accel_plan* p, Op& op)
                     c.scale_h2s = static_cast<const float*>(dsh);
                 }
             }
-        } else if (c.force_tile == CONV_TILE_STEM || c.force_tile == CONV_TILE_STEM_B3) {
+        } else if (forced_w == CONV_W_WSTEM || forced_w == CONV_W_WSTEMB) {
             return fail(ACCEL_ERR_ARG, "conv %s: the stem kernel takes 7x7 / stride 2 / pad 3 layers on 3-channel images with 64 "
                                        "output channels only", op.name.c_str());
         }
     }
     {
         // weight-stationary streaming kernel for the 1x1 expand layers with K = 64 / 128 (ACCEL_WITHHOLD=ws1x1 withholds it)
-        const bool want = !withheld("ws1x1") || c.force_tile == CONV_TILE_WS;
+        const bool want = !withheld("ws1x1") || forced_w == CONV_W_WWS;
         c.y2 = op.c.set ? op.c.ptr : nullptr;
         if (want && !cols && cin == cin_pad && conv_ws_eligible(c)) {
             std::vector<float> ww(conv_ws_pack_floats(cin, cout_store), 0.f);
@@ -778,7 +780,7 @@ static int finalize_conv(accel_plan* p, Op& op)
             if ((rc = dev_upload(p, ww.data(), ww.size() * sizeof(float), &dw))) return rc;
             c.wws = static_cast<const float*>(dw);
             c.wws_bytes = (unsigned)(ww.size() * sizeof(float));
-        } else if (c.force_tile == CONV_TILE_WS) {
+        } else if (forced_w == CONV_W_WWS) {
             return fail(ACCEL_ERR_ARG, "conv %s: the weight-stationary kernel takes 1x1 / stride 1 layers from 64 to a multiple of 256 "
                                        "or from 128 to a multiple of 128 channels (ReLU or no activation, one output) only", op.name.c_str());
         }
@@ -1133,9 +1135,10 @@ static bool conv_has_h2_form(const ConvParams& c) { return c.wh2r || c.wubh || c
 static bool conv_runs_h2(const ConvParams& c)
 {
     if (c.f16 || c.narrow) return false;
-    const int t = c.force_tile;
-    return ((t == CONV_TILE_WINO_B3 || t == CONV_TILE_WINO_B3U || t == CONV_TILE_WINO_B3S) && c.wubh) || (t == CONV_TILE_STEM_B3 && c.wstemh) ||
-           (((t >= CONV_TILE_B3R && t < CONV_TILE_B3R + 6) || (t >= 90 && t <= 96)) && c.wh2r);      // (90-96: the ablation builds of geometry 76, diagnostics library only)
+    const ConvTile* t = conv_tile_row(c.force_tile);
+    if (!t) return false;
+    return (t->weights == CONV_W_WUB && c.wubh) || (t->weights == CONV_W_WSTEMB && c.wstemh) ||
+           ((t->weights == CONV_W_WB3R || t->weights == CONV_W_WH2R) && t->family != CONV_FAM_B3D && c.wh2r);      // conv_b3r.hip (its ablations too) and conv_halo.hip
 }
 
 static int assign_range_slots(accel_plan* p)
@@ -1201,8 +1204,8 @@ static void resolve_range_flags(accel_plan* p, bool (*counts)(const ConvParams&)
             // (half outputs: the lowering keeps a buffer half only if every reader is an f16-mode convolution -- none has an fp16x2 form)
             // and the f16-mode kernels of conv_b3d.hip have no range epilogue: a reader of their output measures its view)
             {
-                const int t = op.conv.force_tile;
-                const bool ep = !op.conv.y_half && !(t >= CONV_TILE_B3D && t < CONV_TILE_B3D + CONV_TILE_B3D_N) && !(op.conv.x_half || op.conv.res_half);
+                const ConvTile* t = conv_tile_row(op.conv.force_tile);
+                const bool ep = !op.conv.y_half && !(t && t->family == CONV_FAM_B3D) && !(op.conv.x_half || op.conv.res_half);
                 op.conv.yr = ep ? addr(op.rs_out) : nullptr;
                 op.conv.y2r = ep ? addr(op.rs_out2) : nullptr;
                 wrote(op.rs_out, ep); wrote(op.rs_out2, ep);
@@ -1333,6 +1336,57 @@ static size_t conv_apply(ConvParams& c, int tile, int split_target, int no_split
     return conv_plan_split(c);
 }
 
+struct Cand { int tile, split_target, no_split; };
+
+// The launch geometries a layer is timed on, in the order they are timed (the first of equals wins).  All of them compute the same
+// contraction.  Ids come from the table in ascending order (conv_tiles.h: CONV_T_TUNE), each as offer() expands it.
+static void conv_candidates(const ConvParams& c, std::vector<Cand>& cs)
+{
+    // t, then t split until ~1024 blocks if that changes the split, then t unsplit if it splits by default
+    auto offer = [&](int t) {
+        cs.push_back({t, 0, 0});
+        ConvParams q = c;
+        const size_t base = conv_apply(q, t, 0, 0);
+        const int ks0 = q.ksplit;
+        if (conv_apply(q, t, 1024, 0) && q.ksplit != ks0) cs.push_back({t, 1024, 0});
+        if (base) cs.push_back({t, 0, 1});
+    };
+    auto offer_each = [&](auto&& takes) {
+        for (int id = 0; id < CONV_TILE_IDS; ++id)
+            if (const ConvTile* t = conv_tile(id); t && (t->flags & CONV_T_TUNE) && takes(*t)) offer(id);
+    };
+    if (c.x_half || c.y_half || c.res_half) {
+        // a layer with half views runs on the fp16 form of conv_b3d.hip; the table says which tiles want more than 64 / 128 channels
+        offer_each([&](const ConvTile& t) {
+            return t.family == CONV_FAM_B3D && !((t.flags & CONV_T_OVER128) && c.Cout_store <= 128) && !((t.flags & CONV_T_OVER64) && c.Cout_store <= 64);
+        });
+    }
+    else if (c.f16 && c.Cout_store <= 32) { cs.push_back({3, 0, 0}); cs.push_back({3, 1024, 0}); }
+    else if (c.Cout_store <= 32) {
+        cs.push_back({4, 0, 0}); cs.push_back({4, 1024, 0}); cs.push_back({9, 0, 0}); cs.push_back({9, 1024, 0}); cs.push_back({3, 0, 0});
+        if (c.wh2r && conv_halo_eligible(c) && !withheld("halo")) cs.push_back({CONV_TILE_HALO, 0, 1});      // the offset branches of res5 (conv_halo.hip)
+    }
+    else {
+        // (a layer that runs in fp16-MFMA mode stays on the fp16 kernel: "operands of every convolution with Cin % 8 == 0 and
+        // more than 4 output channels are rounded to half" is then the exact specification of the mode, which the oracle
+        // restates -- oracle/graphs.py ROUND_F16 -- instead of depending on what the tuner happened to pick)
+        if (c.wu && !c.f16) offer(CONV_TILE_WINO);
+        if (c.wub && !c.f16) offer_each([](const ConvTile& t) { return t.weights == CONV_W_WUB; });
+        if (c.wstem && !c.f16) offer(CONV_TILE_STEM);
+        if (c.wstemb && !c.f16) offer(CONV_TILE_STEM_B3);
+        if (c.wws && !c.f16) offer(CONV_TILE_WS);
+        if (c.wh2r && !c.f16 && conv_halo_eligible(c) && !withheld("halo")) cs.push_back({CONV_TILE_HALO, 0, 1});
+        const bool no_deep = withheld("deep");      // A/B switch: leave the deep-prefetch variants out
+        offer_each([&](const ConvTile& t) {
+            const bool b3r = t.family == CONV_FAM_B3R && c.wb3r;
+            if (t.weights == CONV_W) { if (t.family == CONV_FAM_IGEMM_DEEP && no_deep) return false; }
+            else if (!(b3r || (t.family == CONV_FAM_B3 && c.wb3))) return false;
+            if (c.K_pad % t.bk) return false;      // BK-64 variants need K_pad % 64 == 0
+            return !c.f16 || (t.flags & CONV_T_F16) || (c.f16 == 1 && b3r);
+        });
+    }
+}
+
 static int autotune_plan(accel_plan* p)
 {
     const char* e = getenv("ACCEL_AUTOTUNE");
@@ -1340,7 +1394,6 @@ static int autotune_plan(accel_plan* p)
     hipStream_t st = p->m->ctx->stream;
     tune_cache_load();
     bool tuned_any = false;
-    struct Cand { int tile, split_target, no_split; };
     // pass 1: workspace large enough for every candidate
     std::vector<std::vector<Cand>> cands(p->ops.size());
     size_t ws_need = p->ws_bytes;
@@ -1349,69 +1402,7 @@ static int autotune_plan(accel_plan* p)
         if (op.kind != OP_CONV || op.conv.force_tile >= 0 || op.conv.narrow) continue;
         ConvParams c = op.conv;
         std::vector<Cand>& cs = cands[i];
-        if (c.x_half || c.y_half || c.res_half) {
-            // a layer with half views runs on the fp16 form of conv_b3d.hip: 82 / 83 / 84 / 85 / 88 / 89 by tile shape
-            for (int t : {CONV_TILE_B3D, CONV_TILE_B3D + 1, CONV_TILE_B3D + 2, CONV_TILE_B3D + 3, CONV_TILE_B3D + 6, CONV_TILE_B3D + 7}) {
-                if ((t == CONV_TILE_B3D || t == CONV_TILE_B3D + 1) && c.Cout_store <= 128) continue;      // 256-column tiles
-                if ((t != CONV_TILE_B3D + 6) && c.Cout_store <= 64) continue;                              // 64 channels: the 128x64 tile only
-                cs.push_back({t, 0, 0});
-                ConvParams q = c;
-                const size_t base = conv_apply(q, t, 0, 0);
-                const int ks0 = q.ksplit;
-                if (conv_apply(q, t, 1024, 0) && q.ksplit != ks0) cs.push_back({t, 1024, 0});
-                if (base) cs.push_back({t, 0, 1});
-            }
-        }
-        else if (c.f16 && c.Cout_store <= 32) { cs.push_back({3, 0, 0}); cs.push_back({3, 1024, 0}); }
-        else if (c.Cout_store <= 32) {
-            cs.push_back({4, 0, 0}); cs.push_back({4, 1024, 0}); cs.push_back({9, 0, 0}); cs.push_back({9, 1024, 0}); cs.push_back({3, 0, 0});
-            if (c.wh2r && conv_halo_eligible(c) && !withheld("halo")) cs.push_back({CONV_TILE_HALO, 0, 1});      // the offset branches of res5 (conv_halo.hip)
-        }
-        else {
-            // (a layer that runs in fp16-MFMA mode stays on the fp16 kernel: "operands of every convolution with Cin % 8 == 0 and
-            // more than 4 output channels are rounded to half" is then the exact specification of the mode, which the oracle
-            // restates -- oracle/graphs.py ROUND_F16 -- instead of depending on what the tuner happened to pick)
-            if (c.wu && !c.f16) {
-                cs.push_back({CONV_TILE_WINO, 0, 0});
-                ConvParams q = c;
-                const size_t base = conv_apply(q, CONV_TILE_WINO, 0, 0);
-                const int ks0 = q.ksplit;
-                if (conv_apply(q, CONV_TILE_WINO, 1024, 0) && q.ksplit != ks0) cs.push_back({CONV_TILE_WINO, 1024, 0});
-                if (base) cs.push_back({CONV_TILE_WINO, 0, 1});
-            }
-            if (c.wub && !c.f16) {
-                for (int wt : {CONV_TILE_WINO_B3, CONV_TILE_WINO_B3U, CONV_TILE_WINO_B3S}) {
-                    cs.push_back({wt, 0, 0});
-                    ConvParams q = c;
-                    const size_t base = conv_apply(q, wt, 0, 0);
-                    const int ks0 = q.ksplit;
-                    if (conv_apply(q, wt, 1024, 0) && q.ksplit != ks0) cs.push_back({wt, 1024, 0});
-                    if (base) cs.push_back({wt, 0, 1});
-                }
-            }
-            if (c.wstem && !c.f16) cs.push_back({CONV_TILE_STEM, 0, 0});
-            if (c.wstemb && !c.f16) cs.push_back({CONV_TILE_STEM_B3, 0, 0});
-            if (c.wws && !c.f16) cs.push_back({CONV_TILE_WS, 0, 0});
-            if (c.wh2r && !c.f16 && conv_halo_eligible(c) && !withheld("halo")) cs.push_back({CONV_TILE_HALO, 0, 1});
-            const int nb3 = c.wb3 ? 5 : 0;
-            static const int tiles[] = {0, 1, 2, 3, 5, 6, 7, 8, 10, 11, 12, 13, 31, 32, 33, 34, 35,
-                                        CONV_TILE_B3, CONV_TILE_B3 + 1, CONV_TILE_B3 + 2, CONV_TILE_B3 + 3, CONV_TILE_B3 + 4, CONV_TILE_B3 + 5,
-                                        CONV_TILE_B3R, CONV_TILE_B3R + 1, CONV_TILE_B3R + 3, CONV_TILE_B3R + 4, CONV_TILE_B3R + 5};
-            const bool no_deep = withheld("deep");
-            for (int t : tiles) {
-                if (t >= CONV_TILE_B3 && t < CONV_TILE_B3R && !nb3) continue;
-                if (t >= CONV_TILE_B3R && !c.wb3r) continue;
-                if (no_deep && t >= 31 && t <= 35) continue;   // A/B switch: leave the deep-prefetch variants out
-                if (c.K_pad % conv_tile_bk(t)) continue;      // BK-64 variants need K_pad % 64 == 0
-                if (c.f16 && !(t <= 3 || t == 10 || (c.f16 == 1 && t >= CONV_TILE_B3R && c.wb3r))) continue;
-                cs.push_back({t, 0, 0});
-                ConvParams q = c;
-                const size_t base = conv_apply(q, t, 0, 0);
-                const int ks0 = q.ksplit;
-                if (conv_apply(q, t, 1024, 0) && q.ksplit != ks0) cs.push_back({t, 1024, 0});
-                if (base) cs.push_back({t, 0, 1});
-            }
-        }
+        conv_candidates(c, cs);
         if (const char* fw = getenv("ACCEL_WB3_FORCE"); fw && c.wub && !c.f16) {
             // diagnostics: every layer that can take 41 / 42 / 43, does.  The geometry goes straight into the layer's parameters:
             // nothing is looked up in, inserted into or erased from the process-wide launch-geometry table (a forced run used to

@@ -1094,7 +1094,7 @@ static hipError_t launch_b3(const ConvParams& p0, hipStream_t st)
 int conv_pick_tile(const ConvParams& p)
 {
     if (p.force_tile >= 0) return p.force_tile;
-    if (p.x_half || p.y_half || p.res_half) return p.Cout_store <= 64 ? CONV_TILE_B3D + 6 : CONV_TILE_B3D + 2;   // half views: conv_b3d.hip only
+    if (p.x_half || p.y_half || p.res_half) return p.Cout_store <= 64 ? CONV_TILE_HALF_NARROW : CONV_TILE_HALF;
     const long classes = p.deconv2x ? 4 : 1;
     const int cs = p.Cout_store;
     if (cs <= 32) return p.f16 ? 3 : 4;                  // 128x32 (fp32) / 64x64 (fp16 path has no 32-wide tile)
@@ -1120,257 +1120,170 @@ hipError_t launch_splitk_reduce(const ConvParams& p, int classes, hipStream_t st
     return hipGetLastError();
 }
 
-int conv_tile_bk(int tile) { return tile == 13 ? 64 : tile == 15 ? 16 : 32; }
-
-// launch-geometry ids this build carries (all of them compute the same contraction)
-bool conv_tile_valid(int tile)
-{
-#ifdef ACCEL_CONV_DIAG
-    if ((tile >= 20 && tile <= 30) || (tile >= 90 && tile <= 96)) return true;
-#endif
-    return (tile >= 0 && tile <= 19) || (tile >= 31 && tile <= 35) || tile == CONV_TILE_WINO || tile == CONV_TILE_WINO_B3 || tile == CONV_TILE_WINO_B3U || tile == CONV_TILE_WINO_B3S || tile == CONV_TILE_STEM || tile == CONV_TILE_STEM_B3 || tile == CONV_TILE_WS || tile == CONV_TILE_HALO ||
-           (tile >= CONV_TILE_B3 && tile < CONV_TILE_B3 + 8) || (tile >= CONV_TILE_B3R + 3 && tile <= CONV_TILE_B3R + 5) ||
-           (tile >= CONV_TILE_B3D && tile < CONV_TILE_B3D + CONV_TILE_B3D_N);
-}
-
-static void tile_dims(int tile, int& bm, int& bn)
-{
-    static const int BMs[20] = {128, 128, 64, 64, 128, 128, 128, 64, 64, 128, 128, 128, 64, 64, 256, 128, 128, 64, 128, 64};
-    static const int BNs[20] = {128, 64, 128, 64, 32, 128, 64, 128, 64, 32, 128, 64, 128, 64, 128, 128, 128, 64, 128, 64};
-    if (tile == CONV_TILE_B3 + 5) { bm = 256; bn = 128; return; }
-    if (tile == CONV_TILE_B3R || (tile >= 90 && tile <= 96)) { bm = 128; bn = 128; return; }
-    if (tile == CONV_TILE_B3R + 1) { bm = 128; bn = 64; return; }
-    if (tile == CONV_TILE_B3R + 3 || tile == CONV_TILE_B3R + 4) { bm = 128; bn = 256; return; }
-    if (tile == CONV_TILE_B3R + 5) { bm = 128; bn = 128; return; }
-    if (tile == CONV_TILE_B3D || tile == CONV_TILE_B3D + 4) { bm = 256; bn = 256; return; }
-    if (tile == CONV_TILE_B3D + 1 || tile == CONV_TILE_B3D + 5) { bm = 128; bn = 256; return; }
-    if (tile == CONV_TILE_B3D + 2 || tile == CONV_TILE_B3D + 3) { bm = 128; bn = 128; return; }
-    if (tile == CONV_TILE_B3D + 6) { bm = 128; bn = 64; return; }
-    if (tile == CONV_TILE_B3D + 7) { bm = 256; bn = 128; return; }
-    if (tile >= CONV_TILE_B3 && tile < CONV_TILE_B3 + 5) { static const int g[5] = {0, 1, 2, 3, 10}; tile = g[tile - CONV_TILE_B3]; }
-    if (tile >= 31 && tile <= 35) { static const int g[5] = {3, 0, 2, 1, 4}; tile = g[tile - 31]; }   // deep-prefetch variants
-    if (tile >= 20) tile = (tile == 23 || (tile >= 26 && tile != 29)) ? 3 : 0;
-    if (tile < 0 || tile > 19) tile = 3;
-    bm = BMs[tile]; bn = BNs[tile];
-}
-
-// Fill the chip when the output grid alone cannot: split K across blockIdx.z.
+// Fill the chip when the output grid alone cannot: split K across blockIdx.z (Winograd: blockIdx.y, raw partial OUTPUTS -- the
+// output transform is linear -- that the ordinary split-K reduce kernel sums and finishes).  The one rule: a grid of `blocks` blocks
+// with `KT` K steps is split until it has about `target` blocks, slices of at least 4 steps (`even`: of an even number of steps).
 // Returns the workspace bytes the launch needs (0 = no split).
 size_t conv_plan_split(ConvParams& p)
 {
     p.ksplit = 1; p.kt_per_split = 0;
     if (p.no_split || p.narrow) return 0;
-    int bm, bn;
     const int tile = conv_pick_tile(p);
-    if (tile == CONV_TILE_STEM || tile == CONV_TILE_STEM_B3 || tile == CONV_TILE_WS || tile == CONV_TILE_HALO) return 0;
-    if (tile == CONV_TILE_WINO) {
-        // Winograd blocks own 64 tiles (256 pixels) x 64 channels; the K loop runs in steps of 8 channels, unrolled by 2.
-        // Splitting it over blockIdx.y leaves raw partial OUTPUTS (the output transform is linear) that the ordinary
-        // split-K reduce kernel sums and finishes.
-        const long blocks = ((p.M / 4 + 63) / 64) * (long)conv_wino_rows(p.Cout_store) / 64;
-        const int KT = p.Cin / 8, min_steps = 4;
-        const int min_blocks = p.split_target > 0 ? p.split_target : 256;
-        const int target = p.split_target > 0 ? p.split_target : 512;
-        if (blocks >= min_blocks || KT < 2 * min_steps) return 0;
-        int want = (int)((target + blocks - 1) / blocks);
-        int ks = want < KT / min_steps ? want : KT / min_steps;
-        if (ks < 2) return 0;
-        p.kt_per_split = ((KT + ks - 1) / ks + 1) / 2 * 2;             // even: the K loop is unrolled by 2
-        p.ksplit = (KT + p.kt_per_split - 1) / p.kt_per_split;
-        if (p.ksplit < 2) { p.ksplit = 1; p.kt_per_split = 0; return 0; }
-        return (size_t)p.ksplit * p.M * p.Cout_store * sizeof(float);
+    const ConvTile& t = conv_tile_planned(tile);
+    if (t.flags & CONV_T_NOSPLIT) return 0;
+    long classes = p.deconv2x ? 4 : 1, blocks;
+    int KT, target = 768;
+    bool even = false;
+    switch (t.family) {
+    case CONV_FAM_WINO: case CONV_FAM_WINO_B3: case CONV_FAM_WINO_B3U: case CONV_FAM_WINO_B3S:
+        // blocks own 64 tiles (256 pixels; 42 / 43: rectangles of tiles, counted by their launchers) x 64 channels
+        blocks = (t.family == CONV_FAM_WINO_B3U ? conv_wino_b3u_blocks(p, nullptr) : t.family == CONV_FAM_WINO_B3S ? conv_wino_b3s_blocks(p, nullptr) : (long)((p.M / 4 + 63) / 64)) *
+                 (long)conv_wino_rows(p.Cout_store) / t.bn;
+        KT = p.Cin / t.bk;
+        target = 512;
+        even = t.family == CONV_FAM_WINO;      // the K loop of conv_wino.hip is unrolled by 2
+        classes = 1;
+        break;
+    default:
+        blocks = classes * ((p.M + t.bm - 1) / t.bm) * ((p.Cout_store + t.bn - 1) / t.bn);
+        KT = p.K_pad / t.bk;
+        // the fp16 form of conv_b3d.hip works in stages of up to four half steps (two K steps): a split-K range ends on a stage boundary
+        even = t.family == CONV_FAM_B3D && p.f16 == 1;
+        break;
     }
-    if (tile == CONV_TILE_WINO_B3 || tile == CONV_TILE_WINO_B3U || tile == CONV_TILE_WINO_B3S) {
-        // conv_wino_b3.hip: blocks of 64 tiles x 64 channels, K steps of 16 channels; raw partial outputs as for tile 40
-        const long blocks = (tile == CONV_TILE_WINO_B3U ? conv_wino_b3u_blocks(p, nullptr) : tile == CONV_TILE_WINO_B3S ? conv_wino_b3s_blocks(p, nullptr) : (long)((p.M / 4 + 63) / 64)) * (long)conv_wino_rows(p.Cout_store) / 64;
-        const int KT = p.Cin / 16, min_steps = 4;
-        const int min_blocks = p.split_target > 0 ? p.split_target : 256;
-        const int target = p.split_target > 0 ? p.split_target : 512;
-        if (blocks >= min_blocks || KT < 2 * min_steps) return 0;
-        int want = (int)((target + blocks - 1) / blocks);
-        int ks = want < KT / min_steps ? want : KT / min_steps;
-        if (ks < 2) return 0;
-        p.kt_per_split = (KT + ks - 1) / ks;
-        p.ksplit = (KT + p.kt_per_split - 1) / p.kt_per_split;
-        if (p.ksplit < 2) { p.ksplit = 1; p.kt_per_split = 0; return 0; }
-        return (size_t)p.ksplit * p.M * p.Cout_store * sizeof(float);
-    }
-    tile_dims(tile, bm, bn);
-    const long classes = p.deconv2x ? 4 : 1;
-    const long blocks = classes * ((p.M + bm - 1) / bm) * ((p.Cout_store + bn - 1) / bn);
-    const int KT = p.K_pad / conv_tile_bk(tile);
     const int min_blocks = p.split_target > 0 ? p.split_target : 256;
-    const int target = p.split_target > 0 ? p.split_target : 768;
+    if (p.split_target > 0) target = p.split_target;
     const int min_steps = 4;
     if (blocks >= min_blocks || KT < 2 * min_steps) return 0;
     int want = (int)((target + blocks - 1) / blocks);
     int ks = want < KT / min_steps ? want : KT / min_steps;
     if (ks < 2) return 0;
     p.kt_per_split = (KT + ks - 1) / ks;
-    // the fp16 form of conv_b3d.hip works in stages of up to four half steps (two K steps): a split-K range ends on a stage boundary
-    if (tile >= CONV_TILE_B3D && tile < CONV_TILE_B3D + CONV_TILE_B3D_N && p.f16 == 1) p.kt_per_split = (p.kt_per_split + 1) / 2 * 2;
+    if (even) p.kt_per_split = (p.kt_per_split + 1) / 2 * 2;
     p.ksplit = (KT + p.kt_per_split - 1) / p.kt_per_split;
     if (p.ksplit < 2) { p.ksplit = 1; p.kt_per_split = 0; return 0; }
     return (size_t)p.ksplit * classes * p.M * p.Cout_store * sizeof(float);
 }
 
+// The operands the launcher of a family expects, made from the layer's in this one place (q starts as a copy of p).  `own` false:
+// the family does not take the layer in its mode -- the layer runs the kernel of its mode on the id's shape (conv_tiles.h, quirks)
+static hipError_t conv_prepare(const ConvParams& p, const ConvTile& t, ConvParams& q, bool& own)
+{
+    const bool half_views = p.x_half || p.y_half || p.res_half;
+    auto plane = [&](const void* w) { q.w = static_cast<const float*>(w); q.w_bytes = p.w_bytes / 2; };      // one 16-bit plane of one parity class
+    auto h2 = [&](const float* scale) { q.scale = scale; q.xr = p.xr_slot; q.f16 = 3; };      // the fp16x2 form: two half planes per operand, three products
+    own = true;
+    switch (t.family) {
+    case CONV_FAM_WINO: case CONV_FAM_STEM: case CONV_FAM_WS:
+        return hipSuccess;
+    case CONV_FAM_WINO_B3: case CONV_FAM_WINO_B3U: case CONV_FAM_WINO_B3S:
+        if (p.wubh && !p.f16) { q.wub = p.wubh; q.wub_bytes = p.wub_bytes / 3 * 2; h2(p.scale_h2w); }      // two half planes of U
+        return hipSuccess;
+    case CONV_FAM_STEM_B3:
+        if (p.wstemh && !p.f16) { q.wstemb = p.wstemh; h2(p.scale_h2s); }
+        return hipSuccess;
+    case CONV_FAM_HALO:      // fp16x2 form only: the two half planes of conv_b3r.hip
+        if (p.f16 || !p.wh2r || half_views) return hipErrorInvalidValue;
+        plane(p.wh2r); h2(p.scale_h2);
+        return hipSuccess;
+    case CONV_FAM_B3D:       // the one-plane fp16 form of an f16-mode layer, both operands by LDS-DMA (fp32 / half views)
+        if (!p.wb3r || p.f16 != 1) return hipErrorInvalidValue;
+        q.w = static_cast<const float*>(p.wb3r);
+        return hipSuccess;
+    default: break;
+    }
+    if (half_views) return hipErrorInvalidValue;      // no other kernel reads or writes half views
+    switch (t.family) {
+    case CONV_FAM_B3R: case CONV_FAM_DIAG_B3R:
+        if (p.f16 == 1 && t.family == CONV_FAM_B3R) {
+            // fp16-MFMA mode on the staging of conv_b3r.hip: one plane of half-rounded weights in MFMA fragment order
+            if (!p.wb3r) return hipErrorInvalidValue;
+            q.w = static_cast<const float*>(p.wb3r);
+            return hipSuccess;
+        }
+        if (!p.f16 && p.wh2r) { plane(p.wh2r); h2(p.scale_h2); return hipSuccess; }
+        if (!p.f16) {
+            if (!p.wb3r) return hipErrorInvalidValue;
+            plane(p.wb3r); q.f16 = 2;
+            return hipSuccess;
+        }
+        break;
+    case CONV_FAM_B3:
+        // an fp32 layer on the bf16 matrix cores: same inputs and outputs, the products taken as 3 x bf16 splits
+        if (!p.f16) {
+            if (!p.wb3) return hipErrorInvalidValue;
+            plane(p.wb3); q.f16 = 2;
+            return hipSuccess;
+        }
+        break;
+    default: break;
+    }
+    own = false;
+    if (!p.f16) {
+        if (p.K_pad % t.bk) return hipErrorInvalidValue;
+        if (t.family == CONV_FAM_IGEMM_DMA && p.Cin % 32) return hipErrorInvalidValue;   // DMA variants need wave-uniform taps per K step
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_conv_igemm(const ConvParams& p, hipStream_t st)
 {
-    // tile ids: 0-4 = geometry {128x128, 128x64, 64x128, 64x64, 128x32} with the plain schedule;
-    // 5-9 the same geometries with the software-pipelined schedule (MID = 2);
-    // +10 = 8-wave / BK-64 experiments (same geometry order)
     if (p.narrow) return launch_conv_narrow(p, st);
-    if (p.force_tile == CONV_TILE_WINO) return launch_conv_wino(p, st);
-    if (p.force_tile == CONV_TILE_WINO_B3 || p.force_tile == CONV_TILE_WINO_B3U || p.force_tile == CONV_TILE_WINO_B3S) {
-        ConvParams q = p;
-        if (p.wubh && !p.f16) {      // the fp16x2 form: two half planes of U, three products
-            q.wub = p.wubh;
-            q.wub_bytes = p.wub_bytes / 3 * 2;
-            q.scale = p.scale_h2w;
-            q.xr = p.xr_slot;
-            q.f16 = 3;
-        }
-        if (p.force_tile == CONV_TILE_WINO_B3S) return launch_conv_wino_b3s(q, st);
-        return launch_conv_wino_b3(q, st, p.force_tile == CONV_TILE_WINO_B3U);
-    }
-    if (p.force_tile == CONV_TILE_STEM) return launch_conv_stem(p, st);
-    if (p.force_tile == CONV_TILE_STEM_B3) {
-        if (p.wstemh && !p.f16) {      // the fp16x2 form
-            ConvParams q = p;
-            q.wstemb = p.wstemh;
-            q.scale = p.scale_h2s;
-            q.xr = p.xr_slot;
-            q.f16 = 3;
-            return launch_conv_stem_b3(q, st);
-        }
-        return launch_conv_stem_b3(p, st);
-    }
-    if (p.force_tile == CONV_TILE_WS) return launch_conv_ws(p, st);
-    if (p.force_tile == CONV_TILE_HALO) {      // fp16x2 form only: the two half planes of conv_b3r.hip
-        if (p.f16 || !p.wh2r || p.x_half || p.y_half || p.res_half) return hipErrorInvalidValue;
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wh2r);
-        q.w_bytes = p.w_bytes / 2;
-        q.scale = p.scale_h2;
-        q.xr = p.xr_slot;
-        q.f16 = 3;
-        return launch_conv_halo(q, st);
-    }
-    const int b3d_tile = (p.force_tile < 0 && (p.x_half || p.y_half || p.res_half)) ? conv_pick_tile(p) : p.force_tile;
-    if (b3d_tile >= CONV_TILE_B3D && b3d_tile < CONV_TILE_B3D + CONV_TILE_B3D_N) {
-        // conv_b3d.hip: the one-plane fp16 form of an f16-mode layer, both operands by LDS-DMA (fp32 / half views)
-        if (!p.wb3r || p.f16 != 1) return hipErrorInvalidValue;
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wb3r);
-        return launch_conv_b3d(q, b3d_tile, st);
-    }
-    if (p.x_half || p.y_half || p.res_half) return hipErrorInvalidValue;      // no other kernel reads or writes half views
-    if (p.force_tile >= CONV_TILE_B3R && p.force_tile < CONV_TILE_B3R + 6 && p.f16 == 1) {
-        // fp16-MFMA mode on the staging of conv_b3r.hip: one plane of half-rounded weights in MFMA fragment order
-        if (!p.wb3r) return hipErrorInvalidValue;
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wb3r);
-        return launch_conv_b3r(q, p.force_tile, st);
-    }
-    if (((p.force_tile >= CONV_TILE_B3R && p.force_tile < CONV_TILE_B3R + 6) || (p.force_tile >= 90 && p.force_tile <= 96)) && !p.f16 && p.wh2r) {      // (90-96: ablations, diagnostics build)
-        // the fp16x2 form of the same staging: two half planes per operand, three products
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wh2r);
-        q.w_bytes = p.w_bytes / 2;
-        q.scale = p.scale_h2;
-        q.xr = p.xr_slot;
-        q.f16 = 3;
-        return launch_conv_b3r(q, p.force_tile, st);
-    }
-    if (((p.force_tile >= CONV_TILE_B3R && p.force_tile < CONV_TILE_B3R + 6) || (p.force_tile >= 90 && p.force_tile <= 96)) && !p.f16) {
-        if (!p.wb3r) return hipErrorInvalidValue;
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wb3r);
-        q.w_bytes = p.w_bytes / 2;               // one bf16 plane of one parity class
-        q.f16 = 2;
-        return launch_conv_b3r(q, p.force_tile, st);
-    }
-    if (p.force_tile >= CONV_TILE_B3 && p.force_tile < CONV_TILE_B3 + 6 && !p.f16) {
-        // an fp32 layer on the bf16 matrix cores: same inputs and outputs, the products taken as 3 x bf16 splits
-        if (!p.wb3) return hipErrorInvalidValue;
-        ConvParams q = p;
-        q.w = static_cast<const float*>(p.wb3);
-        q.w_bytes = p.w_bytes / 2;               // one bf16 plane of one parity class
-        q.f16 = 2;
-        switch (p.force_tile - CONV_TILE_B3) {
-            case 0: return launch_b3<128, 128, 2, 2>(q, st);
-            case 1: return launch_b3<128, 64, 2, 2>(q, st);
-            case 2: return launch_b3<64, 128, 2, 2>(q, st);
-            case 3: return launch_b3<64, 64, 2, 2>(q, st);
-            case 5: return launch_b3<256, 128, 4, 2>(q, st);     // 92 KB of LDS: one block per CU, 1.5x the flops per byte fetched
-            default: return launch_b3<128, 128, 2, 4>(q, st);
-        }
-    }
-    if (p.f16 == 2) {      // fp32 split into three bf16 terms on the bf16 matrix cores: the same geometry ids
-        switch (conv_pick_tile(p)) {
-            case 0: case 5: return launch_b3<128, 128, 2, 2>(p, st);
-            case 1: case 6: return launch_b3<128, 64, 2, 2>(p, st);
-            case 2: case 7: return launch_b3<64, 128, 2, 2>(p, st);
-            case 10: return launch_b3<128, 128, 2, 4>(p, st);
-            default: return launch_b3<64, 64, 2, 2>(p, st);
-        }
-    }
-    if (p.f16) {      // fp16-MFMA path: geometry ids 0-4 / 10-12 map onto the same tile shapes
-        switch (conv_pick_tile(p)) {
-            case 0: case 5: return launch_f16<128, 128, 2, 2>(p, st);
-            case 1: case 6: return launch_f16<128, 64, 2, 2>(p, st);
-            case 2: case 7: return launch_f16<64, 128, 2, 2>(p, st);
-            case 10: return launch_f16<128, 128, 2, 4>(p, st);
-            default: return launch_f16<64, 64, 2, 2>(p, st);   // incl. the narrow-N geometries
-        }
-    }
     const int tile = conv_pick_tile(p);
-    if (p.K_pad % conv_tile_bk(tile)) return hipErrorInvalidValue;
-    if (tile >= 16 && tile <= 19) {
-        if (p.Cin % 32) return hipErrorInvalidValue;   // DMA variants need wave-uniform taps per K step
-        switch (tile) {
-            case 16: return launch_dma<128, 128, 2, 4, 3>(p, st);   // 8 waves, 3-stage ring (96 KB)
-            case 17: return launch_dma<64, 64, 2, 2, 3>(p, st);     // 4 waves, 3 stages (48 KB)
-            case 18: return launch_dma<128, 128, 2, 2, 2>(p, st);   // 4 waves, 2 stages (64 KB)
-            default: return launch_dma<64, 64, 2, 2, 4>(p, st);     // 19: 4 stages (64 KB)
+    const ConvTile* t = conv_tile(tile);
+    ConvParams q = p;
+    bool own = false;
+    if (t) {
+        if (hipError_t e = conv_prepare(p, *t, q, own); e != hipSuccess) return e;
+    } else if (p.x_half || p.y_half || p.res_half) return hipErrorInvalidValue;
+    if (own) {
+        switch (t->family) {
+        case CONV_FAM_WINO: return launch_conv_wino(q, st);
+        case CONV_FAM_WINO_B3: return launch_conv_wino_b3(q, st, false);
+        case CONV_FAM_WINO_B3U: return launch_conv_wino_b3(q, st, true);
+        case CONV_FAM_WINO_B3S: return launch_conv_wino_b3s(q, st);
+        case CONV_FAM_STEM: return launch_conv_stem(q, st);
+        case CONV_FAM_STEM_B3: return launch_conv_stem_b3(q, st);
+        case CONV_FAM_WS: return launch_conv_ws(q, st);
+        case CONV_FAM_HALO: return launch_conv_halo(q, st);
+        case CONV_FAM_B3D: return launch_conv_b3d(q, tile, st);
+        case CONV_FAM_B3R: case CONV_FAM_DIAG_B3R: return launch_conv_b3r(q, tile, st);
+        default: break;      // CONV_FAM_B3: below, on its own shape
+        }
+    }
+    if (q.f16) {
+        // bf16x3 (2: fp32 split into three bf16 terms on the bf16 matrix cores) and fp16-MFMA mode: the id's shape16 (64x64 for an id
+        // without a row, and for an id of the b3 family in a mode the family does not take)
+        const int shape = (!t || (t->family == CONV_FAM_B3 && !own)) ? 3 : t->shape16;
+        if (q.f16 == 2) {
+            switch (shape) {
+#define B3_CASE(ROW, BM, BN, WGM, WGN) case ROW: return launch_b3<BM, BN, WGM, WGN>(q, st);
+                CONV_SHAPES16(B3_CASE)
+#undef B3_CASE
+                case 5: return launch_b3<256, 128, 4, 2>(q, st);
+                default: return hipErrorInvalidValue;
+            }
+        }
+        switch (shape) {
+#define F16_CASE(ROW, BM, BN, WGM, WGN) case ROW: return launch_f16<BM, BN, WGM, WGN>(q, st);
+            CONV_SHAPES16(F16_CASE)
+#undef F16_CASE
+            default: return hipErrorInvalidValue;
         }
     }
     switch (tile) {
-        case 0: return launch_cfg<128, 128, 2, 2, 32, 0>(p, st);
-        case 1: return launch_cfg<128, 64, 2, 2, 32, 0>(p, st);
-        case 2: return launch_cfg<64, 128, 2, 2, 32, 0>(p, st);
-        case 3: return launch_cfg<64, 64, 2, 2, 32, 0>(p, st);
-        case 4: return launch_cfg<128, 32, 4, 1, 32, 0>(p, st);
-        case 5: return launch_cfg<128, 128, 2, 2, 32, 2>(p, st);
-        case 6: return launch_cfg<128, 64, 2, 2, 32, 2>(p, st);
-        case 7: return launch_cfg<64, 128, 2, 2, 32, 2>(p, st);
-        case 8: return launch_cfg<64, 64, 2, 2, 32, 2>(p, st);
-        case 9: return launch_cfg<128, 32, 4, 1, 32, 2>(p, st);
-        case 10: return launch_cfg<128, 128, 2, 4, 32, 2>(p, st);   // 8 waves, wave tile 64x32
-        case 11: return launch_cfg<128, 64, 4, 2, 32, 2>(p, st);    // 8 waves, wave tile 32x32
-        case 12: return launch_cfg<64, 128, 2, 4, 32, 2>(p, st);    // 8 waves, wave tile 32x32
-        case 13: return launch_cfg<64, 64, 2, 2, 64, 2>(p, st);     // BK 64
-        case 14: return launch_cfg<256, 128, 4, 2, 32, 2>(p, st);   // 8 waves, wave tile 64x64 (110 KB LDS, 1 block/CU)
-        case 15: return launch_cfg<128, 128, 2, 2, 16, 0>(p, st);   // BK 16: half the LDS, 4 blocks/CU
-        case 31: return launch_cfg<64, 64, 2, 2, 32, 3>(p, st);     // 31-35: deep-prefetch schedule (MID = 3)
-        case 32: return launch_cfg<128, 128, 2, 4, 32, 3>(p, st);
-        case 33: return launch_cfg<64, 128, 2, 4, 32, 3>(p, st);
-        case 34: return launch_cfg<128, 64, 4, 2, 32, 3>(p, st);
-        case 35: return launch_cfg<128, 32, 4, 1, 32, 3>(p, st);
+#define IGEMM_CASE(ID, BM, BN, WGM, WGN, BK, MID, S16, FLAGS) case ID: return launch_cfg<BM, BN, WGM, WGN, BK, MID>(q, st);
+#define DMA_CASE(ID, BM, BN, WGM, WGN, STAGES) case ID: return launch_dma<BM, BN, WGM, WGN, STAGES>(q, st);
+        CONV_IGEMM_TILES(IGEMM_CASE)
+        CONV_DMA_TILES(DMA_CASE)
+#undef IGEMM_CASE
+#undef DMA_CASE
 #ifdef ACCEL_CONV_DIAG
         // timing-only ablation variants (they skip loads / stores / barriers and compute WRONG results): compiled into
         // the diagnostics build alone (`make -C accel_amd/csrc diag`, scripts/microbench), never into libaccel_hip.so
-        case 20: return launch_cfg<128, 128, 2, 2, 32, 0, 1>(p, st);   // ablation: no loads
-        case 21: return launch_cfg<128, 128, 2, 2, 32, 0, 3>(p, st);   // ablation: no loads, no barrier
-        case 22: return launch_cfg<128, 128, 2, 2, 32, 0, 2>(p, st);   // ablation: no barrier (racy, timing only)
-        case 23: return launch_cfg<64, 64, 2, 2, 32, 0, 3>(p, st);
-        case 24: return launch_cfg<128, 128, 2, 2, 32, 0, 4>(p, st);   // ablation: loads but no LDS stores
-        case 25: return launch_cfg<128, 128, 2, 2, 32, 0, 8>(p, st);   // ablation: LDS stores but no loads
-        case 26: return launch_cfg<64, 64, 2, 2, 32, 0, 4>(p, st);
-        case 27: return launch_cfg<64, 64, 2, 2, 32, 0, 8>(p, st);
-        case 28: return launch_cfg<64, 64, 2, 2, 32, 0, 1>(p, st);
-        case 29: return launch_cfg<128, 128, 2, 2, 32, 0, 16>(p, st);  // setprio experiment
-        case 30: return launch_cfg<64, 64, 2, 2, 32, 0, 16>(p, st);
+#define DIAG_CASE(ID, BM, BN, WGM, WGN, ABL) case ID: return launch_cfg<BM, BN, WGM, WGN, 32, 0, ABL>(q, st);
+        CONV_IGEMM_DIAG_TILES(DIAG_CASE)
+#undef DIAG_CASE
 #endif
         default: return hipErrorInvalidValue;
     }

@@ -5,6 +5,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "conv_tiles.h"
 
 struct ConvParams {
     const float* x;        // NHWC input view (channel offset already applied)
@@ -52,12 +53,12 @@ struct ConvParams {
     // direct 7x7/2 stem variant (conv_stem.hip, tile id 50): weights pre-arranged per lane
     const float* wstem;    // null: not a 3-channel 7x7/2 stem (or ACCEL_WITHHOLD=stem)
     const void* wstemb;    // the same layer on the bf16 matrix cores (conv_stem_b3.hip, tile id 51): three bf16 planes in fragment order; null: not offered
+    // bf16x3 variant of an fp32 layer (family b3 of conv_tiles.h): the weights once more, split into three bf16 planes
+    const void* wb3;       // null: Cin % 4 != 0, narrow output, or ACCEL_WITHHOLD=split
     // weight-stationary streaming 1x1 variant (conv_1x1ws.hip, tile id 60): weights as the LDS image per column group
-    // bf16x3 variant of an fp32 layer (launch geometries 70-74): the weights once more, split into three bf16 planes
-    const void* wb3;       // null: Cin % 8 != 0, narrow output, or ACCEL_WITHHOLD=split
     const float* wws;      // null: not a 64 -> k*256 / 128 -> k*128 1x1 stride-1 layer (or ACCEL_WITHHOLD=ws1x1)
     unsigned wws_bytes;
-    // second-generation bf16x3 kernel (conv_b3r.hip, launch geometries 76, 77, 79, 80, 81): the three bf16 planes once more, in MFMA
+    // second-generation bf16x3 kernel (conv_b3r.hip, family b3r): the three bf16 planes once more, in MFMA
     // fragment order [class][K step][half step][row][16] (weights go global -> VGPR, never through LDS)
     const void* wb3r;      // null where wb3 is null (or ACCEL_WITHHOLD=b3r)
     const void* wub;       // conv_wino_b3.hip: U = G g G^T as three bf16 planes [plane][C/16][16][wino_rows][16]; null: not offered
@@ -92,8 +93,8 @@ struct ConvParams {
 
 hipError_t launch_conv_igemm(const ConvParams& p, hipStream_t st);
 int conv_pick_tile(const ConvParams& p);
-int conv_tile_bk(int tile);
-bool conv_tile_valid(int tile);
+// launch geometry ids: conv_tiles.h has the table (family, nominal shape, weight copy per id); the names below are the ids other code forces
+bool conv_tile_valid(int tile);          // part of this build
 #define CONV_TILE_WINO 40
 #define CONV_TILE_WINO_B3S 43     // 42 with half the block (32 tiles x 64 channels, 4 wavefronts): two blocks per CU (conv_wino_b3s.hip)
 #define CONV_TILE_WINO_B3U 42     // the same with the union of the block's patches loaded once into an LDS copy (tile blocks 8x8 / 4x16 / 2x32)
@@ -123,12 +124,9 @@ hipError_t launch_conv_stem(const ConvParams& p, hipStream_t st);
 #define CONV_TILE_HALO 78                // conv_halo.hip: 3x3 / stride 1 / dilation 1 or 2 layers with few output channels, the patch staged once with its halo (fp16x2 form only)
 bool conv_halo_eligible(const ConvParams& p);
 hipError_t launch_conv_halo(const ConvParams& p, hipStream_t st);
-#define CONV_TILE_B3 70                  // 70..75: the bf16x3 kernel (fp32 values, bf16 matrix cores) at geometry 0, 1, 2, 3, 10 and 256x128
-#define CONV_TILE_B3R 76                 // conv_b3r.hip: 76 = 128x128 / 2x4 wavefronts, 77 = 128x64 / 2x2, 79 = 128x256 / 2x4, 80 = 128x256 / 1x8, 81 = 128x128 / 1x4
+#define CONV_TILE_B3R 76                 // first id of conv_b3r.hip (its launcher switches over CONV_TILE_B3R + k)
 hipError_t launch_conv_b3r(const ConvParams& p, int tile, hipStream_t st);
-#define CONV_TILE_B3D 82                 // conv_b3d.hip (f16-mode layers only; both operands by LDS-DMA, fp32 or half views): 82 = 256x256 / 4x2 wavefronts,
-                                         // 83 = 128x256 / 4x2, 84 = 128x128 / 4x1, 85 = 128x128 / 2x2, 88 = 128x64 / 4x1, 89 = 256x128 / 4x2 (86 / 87 retired)
-#define CONV_TILE_B3D_N 8
+#define CONV_TILE_B3D 82                 // first id of conv_b3d.hip (f16-mode layers only; both operands by LDS-DMA, fp32 or half views)
 bool conv_b3d_eligible(const ConvParams& p);
 hipError_t launch_conv_b3d(const ConvParams& p, int tile, hipStream_t st);
 #define CONV_TILE_WS 60                  // weight-stationary streaming 1x1 (conv_1x1ws.hip)
