@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "accel_objects.h"
+#include "conv_pack.h"
 #include "kernels.h"
 #include "range.h"
 
@@ -208,14 +209,34 @@ static int dev_upload(accel_plan* p, const void* host, size_t bytes, void** out)
     return 0;
 }
 
+// a host vector as a device copy the plan owns, into the pointer field of a parameter block that it is for
+template <class T, class F>
+static int upload(accel_plan* p, const std::vector<T>& host, F*& field)
+{
+    void* d = nullptr;
+    if (int rc = dev_upload(p, host.data(), host.size() * sizeof(T), &d)) return rc;
+    field = static_cast<F*>(d);
+    return 0;
+}
+
 static const HostParam* get_param(accel_model* m, const std::string& name)
 {
     auto it = m->params.find(name);
     return it == m->params.end() ? nullptr : &it->second;
 }
 
-// BatchNorm inference folding -- identical expressions to oracle orc_bn_fold
-// (MXNet mshadow inference form): scale = g/sqrt(var+eps), shift = beta - g*mean/sqrt(var+eps)
+// the named parameter with n elements (n = 0: any number); `counts`: the refusal says both numbers
+static int param_n(accel_model* m, const std::string& name, size_t n, const HostParam*& out, bool counts = false)
+{
+    out = get_param(m, name);
+    if (!out) return fail(ACCEL_ERR_PARAM, "%s not initialized", name.c_str());
+    if (n && out->numel() != n)
+        return counts ? fail(ACCEL_ERR_PARAM, "shape inconsistent for %s: %zu elements, expected %zu", name.c_str(), out->numel(), n)
+                      : fail(ACCEL_ERR_PARAM, "shape inconsistent for %s", name.c_str());
+    return 0;
+}
+
+// the folded constants (conv_pack.h bn_fold) of the BatchNorm named `bn`, fixg: gamma fixed at 1
 static int bn_fold(accel_model* m, const std::string& bn, float eps, int fixg, int C,
                    std::vector<float>& scale, std::vector<float>& shift)
 {
@@ -227,13 +248,7 @@ static int bn_fold(accel_model* m, const std::string& bn, float eps, int fixg, i
         return fail(ACCEL_ERR_PARAM, "BatchNorm %s: gamma/beta/moving_mean/moving_var not initialized", bn.c_str());
     if ((int)b->numel() != C || (int)mu->numel() != C || (int)var->numel() != C)
         return fail(ACCEL_ERR_PARAM, "BatchNorm %s: expected %d channels, got %zu", bn.c_str(), C, b->numel());
-    scale.assign(C, 0.f); shift.assign(C, 0.f);
-    for (int c = 0; c < C; ++c) {
-        const float gg = fixg ? 1.0f : g->data[c];
-        const float sd = sqrtf(var->data[c] + eps);
-        scale[c] = gg / sd;
-        shift[c] = b->data[c] - (gg * mu->data[c]) / sd;
-    }
+    bn_fold(fixg ? nullptr : g->data.data(), b->data.data(), mu->data.data(), var->data.data(), eps, C, scale, shift);
     return 0;
 }
 
@@ -346,121 +361,44 @@ static int resolve(accel_plan* p, BufRef& r, const char* what, bool half_ok = fa
     return 0;
 }
 
-// ---- weight repacking -------------------------------------------------------
-// fp32 packed weights [classes][rows][K_pad] (+ slack) -> the three bf16 planes of the bf16x3 kernel.  Each weight is split
-// exactly (top 16 bits, then of the residual, twice).  Inside a plane the order is [class][K step of 32][row][32]: the tile a
-// block fetches per K step (BN rows x 32 k) is then ONE contiguous run of BN x 64 bytes -- whole cache lines, where the
-// row-major order gave 64-byte pieces 2 * K_pad bytes apart.
-static void pack_bf16x3(const std::vector<float>& packed, int classes, int rows, int K_pad, std::vector<uint16_t>& out, size_t& plane)
+// ---- a `conv` line into its ConvParams: finalize_conv and its steps (the packers: conv_pack.h) ----------------------------------
+// what the steps hand on: the layer as the plan line states it, and the host copies later steps fold into device vectors
+struct ConvLayer {
+    const HostParam* w = nullptr;
+    int cin = 0, cout = 0, cin_pad = 0, cout_store = 0;
+    int rows = 0;                   // output-channel rows of the generic weight copies: Cout_store rounded up to 128
+    int classes = 1;                // parity classes (deconv2x: 4)
+    bool cols = false;              // mode=cols: the GEMM over the column buffer of dcn_cols
+    int forced_w = -1;              // the weight copy a forced id reads (CONV_W_*); -1: no id forced
+    std::vector<float> packed;      // [class][rows][K_pad] fp32 and the slack
+    std::vector<float> scale;       // the epilogue scale, as uploaded
+    std::vector<int> q;             // ConvParams::wh2r: the exponent per row
+};
+
+// the resolved views of a layer whose shape is known: pointers, strides, M, half flags and the extents the buffer resources get
+static void conv_views(Op& op)
 {
-    const int steps = K_pad / 32;
-    plane = (size_t)classes * rows * K_pad + 2 * (size_t)rows * 32;      // two K steps of slack: the kernel prefetches past the end
-    out.assign(3 * plane, 0);
-    for (int c = 0; c < classes; ++c)
-        for (int n = 0; n < rows; ++n)
-            for (int k = 0; k < K_pad; ++k) {
-                float r = packed[((size_t)c * rows + n) * K_pad + k];
-                const size_t dst = (((size_t)c * steps + k / 32) * rows + n) * 32 + (k & 31);
-                for (int pl = 0; pl < 3; ++pl) {
-                    uint32_t u; memcpy(&u, &r, 4);
-                    u &= 0xFFFF0000u;
-                    out[pl * plane + dst] = (uint16_t)(u >> 16);
-                    float t; memcpy(&t, &u, 4);
-                    r -= t;
-                }
-            }
+    ConvParams& c = op.conv;
+    c.x = op.a.ptr; c.xCs = op.a.Cs; c.H = op.a.H; c.W = op.a.W;
+    c.y = op.b.ptr; c.yCs = op.b.Cs;
+    if (op.c.set) { c.y2 = op.c.ptr; c.y2Cs = op.c.Cs; }
+    if (op.d.set) { c.res = op.d.ptr; c.resCs = op.d.Cs; }
+    c.M = op.a.N * c.Ho * c.Wo;      // batch: the GEMM M dimension runs over (n, oy, ox); images are stacked pixel-major in every view
+    auto extent = [](const BufRef& r, int cuse) {
+        const size_t b = (((size_t)r.N * r.H * r.W - 1) * r.Cs + cuse) * (size_t)r.esize;
+        return (unsigned)(b > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b);
+    };
+    c.x_half = op.a.esize == 2; c.y_half = op.b.esize == 2; c.res_half = op.d.set && op.d.esize == 2;
+    c.x_bytes = extent(op.a, c.Cin > op.a.Cs ? op.a.Cs : c.Cin);
+    c.y_bytes = extent(op.b, c.Cout_store);
+    if (op.c.set) c.y2_bytes = extent(op.c, c.Cout_store);
+    if (op.d.set) c.res_bytes = extent(op.d, c.Cout_store);
 }
 
-// The same three planes in MFMA fragment order for conv_b3r.hip: [class][K step][half step][row][16] -- the 16 bytes lane
-// (row, half) feeds to one v_mfma_f32_32x32x16_bf16 are contiguous (k = 32*step + 16*halfstep + 8*half .. +8), a
-// wavefront's fragment fetch is one contiguous kilobyte.  Two K steps of slack: the kernel prefetches past the end.
-static void pack_bf16x3r(const std::vector<float>& packed, int classes, int rows, int K_pad, std::vector<uint16_t>& out, size_t plane)
+// Step 1: the views and the layer's geometry -- every field of ConvParams that is neither a weight copy, an epilogue vector, the
+// tap table nor the split plan; all that an *_eligible function reads (the list: finalize_conv).
+static int conv_geometry(accel_plan* p, Op& op, ConvLayer& L)
 {
-    const int steps = K_pad / 32;
-    out.assign(3 * plane, 0);
-    for (int c = 0; c < classes; ++c)
-        for (int n = 0; n < rows; ++n)
-            for (int k = 0; k < K_pad; ++k) {
-                float r = packed[((size_t)c * rows + n) * K_pad + k];
-                const int ks = k / 32, kb = (k >> 4) & 1, kk = k & 15;
-                const size_t dst = ((((size_t)c * steps + ks) * 2 + kb) * rows + n) * 16 + kk;
-                for (int pl = 0; pl < 3; ++pl) {
-                    uint32_t u; memcpy(&u, &r, 4);
-                    u &= 0xFFFF0000u;
-                    out[pl * plane + dst] = (uint16_t)(u >> 16);
-                    float t; memcpy(&t, &u, 4);
-                    r -= t;
-                }
-            }
-}
-
-// fp16x2 form of the same fragment-ordered planes (ConvParams::wh2r): every weight as hi + lo, two half terms of w * 2^q[row], the
-// exponent q[row] chosen so that the largest weight of the output channel (over all parity classes) lands in [2^14, 2^15) -- the
-// top of the half range, where lo keeps its full 11 bits (the pair: 2^-23 relative) for every weight down to 2^-16 of the channel's
-// largest; below that the absolute error is 2^-25 of the scaled value, i.e. 2^-39 to 2^-40 of the largest: a bit lost per octave
-// (tests/test_h2_model_cpu.py; on the device, half subnormals included: tests/test_h2_octaves_gpu.py).  The Winograd planes
-// (conv_wino_b3_pack_h2) split U = G g G^T the same way, one octave higher, because they pay that absolute error at 16 positions
-// against |V| <= 4 max|x|.
-// qexp receives q per row; the epilogue scale is multiplied by 2^-q (exact).
-static void pack_h2r(const std::vector<float>& packed, int classes, int rows, int K_pad, std::vector<uint16_t>& out, size_t plane, std::vector<int>& qexp)
-{
-    const int steps = K_pad / 32;
-    out.assign(2 * plane, 0);
-    qexp.assign(rows, 0);
-    for (int n = 0; n < rows; ++n) {
-        float amax = 0.f;
-        for (int c = 0; c < classes; ++c)
-            for (int k = 0; k < K_pad; ++k) amax = std::max(amax, std::fabs(packed[((size_t)c * rows + n) * K_pad + k]));
-        if (amax > 0.f && std::isfinite(amax)) { int e; std::frexp(amax, &e); qexp[n] = 15 - e; }
-    }
-    for (int c = 0; c < classes; ++c)
-        for (int n = 0; n < rows; ++n)
-            for (int k = 0; k < K_pad; ++k) {
-                const float v = std::ldexp(packed[((size_t)c * rows + n) * K_pad + k], qexp[n]);
-                const int ks = k / 32, kb = (k >> 4) & 1, kk = k & 15;
-                const size_t dst = ((((size_t)c * steps + ks) * 2 + kb) * rows + n) * 16 + kk;
-                const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
-                memcpy(&out[dst], &hi, 2);
-                memcpy(&out[plane + dst], &lo, 2);
-            }
-}
-
-// conv weights (Cout, Cin, kh, kw) -> [rows][K_pad], k = (ky*kw + kx)*cin_pad + ci
-static void pack_conv_w(const HostParam& w, int cin_pad, int rows, int K_pad, std::vector<float>& out)
-{
-    const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], kh = (int)w.shape[2], kw = (int)w.shape[3];
-    out.assign((size_t)rows * K_pad, 0.f);
-    for (int co = 0; co < Cout; ++co)
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int ky = 0; ky < kh; ++ky)
-                for (int kx = 0; kx < kw; ++kx)
-                    out[(size_t)co * K_pad + (size_t)(ky * kw + kx) * cin_pad + ci] =
-                        w.data[(((size_t)co * Cin + ci) * kh + ky) * kw + kx];
-}
-
-// deconv 4x4 s2 p1 weights (Cin, Cout, 4, 4) -> [4 classes][rows][K_pad]; class (py,px), tap (ty,tx):
-// ky = 3 - py - 2*ty, kx = 3 - px - 2*tx ; k = (ty*2 + tx)*cin_pad + ci
-static void pack_deconv2x_w(const HostParam& w, int cin_pad, int rows, int K_pad, std::vector<float>& out)
-{
-    const int Cin = (int)w.shape[0], Cout = (int)w.shape[1];
-    out.assign((size_t)4 * rows * K_pad, 0.f);
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            float* base = out.data() + (size_t)(py * 2 + px) * rows * K_pad;
-            for (int co = 0; co < Cout; ++co)
-                for (int ty = 0; ty < 2; ++ty)
-                    for (int tx = 0; tx < 2; ++tx) {
-                        const int ky = 3 - py - 2 * ty, kx = 3 - px - 2 * tx;
-                        for (int ci = 0; ci < Cin; ++ci)
-                            base[(size_t)co * K_pad + (size_t)(ty * 2 + tx) * cin_pad + ci] =
-                                w.data[(((size_t)ci * Cout + co) * 4 + ky) * 4 + kx];
-                    }
-        }
-}
-
-static int finalize_conv(accel_plan* p, Op& op)
-{
-    accel_model* m = p->m;
     const KV& kv = op.kv;
     int rc;
     if ((rc = parse_buf(kv, "in", op.a)) || (rc = parse_buf(kv, "out", op.b)) ||
@@ -470,322 +408,293 @@ static int finalize_conv(accel_plan* p, Op& op)
     if (op.d.set && (rc = resolve(p, op.d, "res", true))) return rc;
 
     const std::string wname = kv_str(kv, "w");
-    const HostParam* w = get_param(m, wname);
+    const HostParam* w = L.w = get_param(p->m, wname);
     if (!w) return fail(ACCEL_ERR_PARAM, "%s not initialized", wname.c_str());
     if (w->shape.size() != 4) return fail(ACCEL_ERR_PARAM, "%s: expected a 4-d weight", wname.c_str());
     const std::string mode = kv_str(kv, "mode", "conv");
-    const bool deconv = mode == "deconv2x";
-    const bool cols = mode == "cols";
+    L.cols = mode == "cols";
     int kh, kw, sh, sw, ph, pw, dh, dw;
     kv_pair(kv, "k", kh, kw, 1, 1);
     kv_pair(kv, "s", sh, sw, 1, 1);
     kv_pair(kv, "p", ph, pw, 0, 0);
     kv_pair(kv, "d", dh, dw, 1, 1);
-    const int cin = (int)kv_int(kv, "cin"), cout = (int)kv_int(kv, "cout");
-    const int cin_pad = roundup(cin, 4);
-    const int cout_store = roundup(cout, 4);
-    const int rows = roundup(cout_store, 128);
+    const int cin = L.cin = (int)kv_int(kv, "cin"), cout = L.cout = (int)kv_int(kv, "cout");
+    const int cin_pad = L.cin_pad = roundup(cin, 4);
+    const int cout_store = L.cout_store = roundup(cout, 4);
+    L.rows = roundup(cout_store, 128);
     if (cout_store > op.b.Cs) return fail(ACCEL_ERR_PLAN, "conv %s: output view too narrow (%d > Cs %d)", op.name.c_str(), cout_store, op.b.Cs);
 
     ConvParams& c = op.conv;
     memset(&c, 0, sizeof c);
-    std::vector<float> packed;
-    if (deconv) {
+    if (mode == "deconv2x") {
         if (w->shape[0] != cin || w->shape[1] != cout || w->shape[2] != 4 || w->shape[3] != 4)
             return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s: need (%d,%d,4,4)", wname.c_str(), cin, cout);
         c.kh = c.kw = 2; c.sh = c.sw = 1; c.dh = c.dw = 1; c.ph = c.pw = 0;
         c.Cin = cin_pad;
         c.K_pad = roundup(4 * cin_pad, 32);
-        pack_deconv2x_w(*w, cin_pad, rows, c.K_pad, packed);
         c.deconv2x = 1;
-        c.w_class_stride = (size_t)rows * c.K_pad;
+        L.classes = 4;
+        c.w_class_stride = (size_t)L.rows * c.K_pad;
         c.Ho = op.a.H; c.Wo = op.a.W;
-        c.yH = op.b.H; c.yW = op.b.W;
         // 4x4/2 pad 1 gives exactly 2h x 2w; the reference's "pad 0 + Crop(offset 1) to the skip tensor" may keep one row /
         // column less when the skip tensor has an odd size (frame sizes that are not multiples of 128): 2h-1 / 2w-1
         if (op.b.H > 2 * op.a.H || op.b.H < 2 * op.a.H - 1 || op.b.W > 2 * op.a.W || op.b.W < 2 * op.a.W - 1)
             return fail(ACCEL_ERR_PLAN, "deconv2x %s: output must be 2x the input (or one row / column less)", op.name.c_str());
     } else {
         int wkh = kh, wkw = kw;
-        if (cols) kv_pair(kv, "wk", wkh, wkw, 3, 3);
+        if (L.cols) kv_pair(kv, "wk", wkh, wkw, 3, 3);
         if (w->shape[0] != cout || w->shape[1] != cin || w->shape[2] != wkh || w->shape[3] != wkw)
             return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s: need (%d,%d,%d,%d) got (%ld,%ld,%ld,%ld)",
                         wname.c_str(), cout, cin, wkh, wkw, (long)w->shape[0], (long)w->shape[1], (long)w->shape[2], (long)w->shape[3]);
         const int Kreal = wkh * wkw * cin_pad;
         c.K_pad = roundup(Kreal, 32);
-        pack_conv_w(*w, cin_pad, rows, c.K_pad, packed);
-        if (cols) { c.kh = c.kw = 1; c.Cin = Kreal; }
+        if (L.cols) { c.kh = c.kw = 1; c.Cin = Kreal; }
         else { c.kh = kh; c.kw = kw; c.Cin = cin_pad; }
         c.sh = sh; c.sw = sw; c.ph = ph; c.pw = pw; c.dh = dh; c.dw = dw;
         c.Ho = op.b.H; c.Wo = op.b.W;
-        c.yH = op.b.H; c.yW = op.b.W;
         const int eh = (op.a.H + 2 * c.ph - c.dh * (c.kh - 1) - 1) / c.sh + 1;
         const int ew = (op.a.W + 2 * c.pw - c.dw * (c.kw - 1) - 1) / c.sw + 1;
         if (eh != op.b.H || ew != op.b.W)
             return fail(ACCEL_ERR_PLAN, "conv %s: output %dx%d does not match geometry %dx%d", op.name.c_str(), op.b.H, op.b.W, eh, ew);
         if (c.Cin > op.a.Cs) return fail(ACCEL_ERR_PLAN, "conv %s: input view narrower than Cin", op.name.c_str());
     }
-    packed.resize(packed.size() + 256, 0.f);   // slack: the pipelined kernel prefetches up to two K steps past the end
+    c.yH = op.b.H; c.yW = op.b.W;
     // fp16-MFMA mode (plan option dtype=f16): only where a K chunk of 8 never straddles two taps
     const char* env_dt = getenv("ACCEL_CONV_DTYPE");   // "f16": also for the single-operator entry points
     const int dflt = (p->f16 == 2 || (env_dt && !strcmp(env_dt, "bf16x3"))) ? 2 : (p->f16 || (env_dt && !strcmp(env_dt, "f16"))) ? 1 : 0;
     const int want_f16 = (int)kv_int(kv, "f16", dflt);
     c.f16 = (want_f16 && c.Cin % (want_f16 == 2 ? 4 : 8) == 0 && cout_store > 4) ? want_f16 : 0;
-    void* dw_ = nullptr;
-    if (c.f16 == 2) {
-        std::vector<uint16_t> pb;
-        pack_bf16x3(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, pb, c.w_plane);
-        if ((rc = dev_upload(p, pb.data(), pb.size() * sizeof(uint16_t), &dw_))) return rc;
-    } else if (c.f16) {
-        std::vector<_Float16> ph(packed.size());
-        for (size_t i = 0; i < packed.size(); ++i) ph[i] = (_Float16)packed[i];
-        if ((rc = dev_upload(p, ph.data(), ph.size() * sizeof(_Float16), &dw_))) return rc;
-        if (!withheld("b3r")) {
-            // the same half-rounded weights once more in MFMA fragment order [class][K step][half step][row][16] for the fp16 form
-            // of conv_b3r.hip (launch geometries 76 / 77 / 79 / 80 / 81 of an f16 layer)
-            const int classes = c.deconv2x ? 4 : 1, steps = c.K_pad / 32;
-            c.w_plane = (size_t)classes * rows * c.K_pad + 2 * (size_t)rows * 32;
-            std::vector<_Float16> pr(c.w_plane, (_Float16)0.f);
-            for (int cl = 0; cl < classes; ++cl)
-                for (int n = 0; n < rows; ++n)
-                    for (int k = 0; k < c.K_pad; ++k)
-                        pr[((((size_t)cl * steps + k / 32) * 2 + ((k >> 4) & 1)) * rows + n) * 16 + (k & 15)] = ph[((size_t)cl * rows + n) * c.K_pad + k];
-            void* d4 = nullptr;
-            if ((rc = dev_upload(p, pr.data(), pr.size() * sizeof(_Float16), &d4))) return rc;
-            c.wb3r = d4;
-        }
-    } else if ((rc = dev_upload(p, packed.data(), packed.size() * sizeof(float), &dw_))) return rc;
-    c.w = static_cast<const float*>(dw_);
-    {
-        // fp32 layers also get their weights as three bf16 planes: the bf16x3 kernel (conv_igemm.hip) is then one more
-        // launch geometry (family b3) of the SAME fp32 convolution for the autotuner (ACCEL_WITHHOLD=split withholds it).  A forced id
-        // that reads one of these copies gets it made (asked of the table's row: the id is checked against this build further down)
-        const ConvTile* ft = conv_tile_row((int)kv_int(kv, "tile", -1));
-        const bool forced_r = ft && (ft->weights == CONV_W_WB3R || ft->weights == CONV_W_WH2R);
-        const bool forced = forced_r || (ft && ft->weights == CONV_W_WB3);
-        if (!c.f16 && c.Cin % 4 == 0 && cout_store > 4 && (!withheld("split") || forced)) {
-            std::vector<uint16_t> pb;
-            pack_bf16x3(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, pb, c.w_plane);
-            void* d3 = nullptr;
-            if ((rc = dev_upload(p, pb.data(), pb.size() * sizeof(uint16_t), &d3))) return rc;
-            c.wb3 = d3;
-            if (!withheld("b3r") || forced_r) {      // the fragment-ordered copy for the second-generation kernel
-                pack_bf16x3r(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, pb, c.w_plane);
-                void* d4 = nullptr;
-                if ((rc = dev_upload(p, pb.data(), pb.size() * sizeof(uint16_t), &d4))) return rc;
-                c.wb3r = d4;
-            }
-        } else if (forced && !(c.f16 == 1 && c.wb3r && forced_r && !(ft->flags & CONV_T_DIAG))) {
-            return fail(ACCEL_ERR_ARG, "conv %s: the bf16x3 kernel takes layers with more than "
-                                       "4 output channels only", op.name.c_str());
-        }
-    }
+    c.w_bytes = (unsigned)((size_t)L.rows * c.K_pad * (c.f16 ? 2 : 4));     // of one plane / class
 
-    // epilogue scale / shift
-    std::vector<float> scale(rows, 0.f), shift(rows, 0.f);
-    for (int i = 0; i < cout; ++i) scale[i] = 1.f;
-    if (kv_has(kv, "bn")) {
-        std::vector<float> s, b;
-        if ((rc = bn_fold(m, kv_str(kv, "bn"), (float)kv_f(kv, "eps", 1e-5), (int)kv_int(kv, "fixg", 0), cout, s, b))) return rc;
-        for (int i = 0; i < cout; ++i) { scale[i] = s[i]; shift[i] = b[i]; }
-    }
-    if (kv_has(kv, "bias")) {
-        const HostParam* bias = get_param(m, kv_str(kv, "bias"));
-        if (!bias) return fail(ACCEL_ERR_PARAM, "%s not initialized", kv_str(kv, "bias").c_str());
-        if ((int)bias->numel() != cout) return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s", kv_str(kv, "bias").c_str());
-        for (int i = 0; i < cout; ++i) shift[i] += bias->data[i] * scale[i];
-    }
-    if (kv_has(kv, "mul")) {
-        const float mul = (float)kv_f(kv, "mul", 1.0);
-        for (int i = 0; i < cout; ++i) { scale[i] *= mul; shift[i] *= mul; }
-    }
-    void *ds = nullptr, *db = nullptr;
-    if ((rc = dev_upload(p, scale.data(), rows * sizeof(float), &ds)) ||
-        (rc = dev_upload(p, shift.data(), rows * sizeof(float), &db))) return rc;
-    c.scale = static_cast<const float*>(ds);
-    c.shift = static_cast<const float*>(db);
-    {
-        const char* sp = getenv("ACCEL_SPLIT");
-        const bool h2 = sp ? !strcmp(sp, "h2") : p->split == 1;
-        if (c.wb3r && !c.f16 && h2) {
-            std::vector<uint16_t> ph;
-            std::vector<int> q;
-            pack_h2r(packed, c.deconv2x ? 4 : 1, rows, c.K_pad, ph, c.w_plane, q);
-            void *dh = nullptr, *dsh = nullptr;
-            if ((rc = dev_upload(p, ph.data(), ph.size() * sizeof(uint16_t), &dh))) return rc;
-            std::vector<float> sh(rows);
-            for (int i = 0; i < rows; ++i) sh[i] = std::ldexp(scale[i], -q[i]);
-            if ((rc = dev_upload(p, sh.data(), rows * sizeof(float), &dsh))) return rc;
-            c.wh2r = dh;
-            c.scale_h2 = static_cast<const float*>(dsh);
-            ++p->n_h2;      // (the layer's input range slot, ConvParams::xr_slot, is assigned once every op is known: assign_range_slots)
-        }
-    }
-    if (op.c.set) {
-        std::vector<float> s2(rows, 0.f), b2(rows, 0.f), s, b;
-        if (kv_has(kv, "bias2")) {          // out2 = relu(v + bias2): the biased, activated copy beside a raw linear output
-            const HostParam* bias = get_param(m, kv_str(kv, "bias2"));
-            if (!bias) return fail(ACCEL_ERR_PARAM, "%s not initialized", kv_str(kv, "bias2").c_str());
-            if ((int)bias->numel() != cout) return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s", kv_str(kv, "bias2").c_str());
-            for (int i = 0; i < cout; ++i) { s2[i] = 1.f; b2[i] = bias->data[i]; }
-        } else {
-            if (!kv_has(kv, "bn2")) return fail(ACCEL_ERR_PLAN, "conv %s: out2 needs bn2 or bias2", op.name.c_str());
-            if ((rc = bn_fold(m, kv_str(kv, "bn2"), (float)kv_f(kv, "eps2", 2e-5), (int)kv_int(kv, "fixg2", 0), cout, s, b))) return rc;
-            for (int i = 0; i < cout; ++i) { s2[i] = s[i]; b2[i] = b[i]; }
-        }
-        void *d2 = nullptr, *e2 = nullptr;
-        if ((rc = dev_upload(p, s2.data(), rows * sizeof(float), &d2)) ||
-            (rc = dev_upload(p, b2.data(), rows * sizeof(float), &e2))) return rc;
-        c.scale2 = static_cast<const float*>(d2);
-        c.shift2 = static_cast<const float*>(e2);
-        c.y2 = op.c.ptr; c.y2Cs = op.c.Cs;
-    }
-    c.x = op.a.ptr; c.xCs = op.a.Cs; c.H = op.a.H; c.W = op.a.W;
-    c.y = op.b.ptr; c.yCs = op.b.Cs;
-    if (op.d.set) { c.res = op.d.ptr; c.resCs = op.d.Cs; }
     c.Cout_store = cout_store;
     c.Cout = cout;
-    // batch: the GEMM M dimension runs over (n, oy, ox); images are stacked pixel-major in every view
-    if (op.b.N != op.a.N || (op.c.set && op.c.N != op.a.N) || (op.d.set && op.d.N != op.a.N))
-        return fail(ACCEL_ERR_PLAN, "conv %s: batch sizes of the views differ", op.name.c_str());
-    c.M = op.a.N * c.Ho * c.Wo;
-    auto extent = [](const BufRef& r, int cuse) {
-        const size_t b = (((size_t)r.N * r.H * r.W - 1) * r.Cs + cuse) * (size_t)r.esize;
-        return (unsigned)(b > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b);
-    };
-    c.x_half = op.a.esize == 2; c.y_half = op.b.esize == 2; c.res_half = op.d.set && op.d.esize == 2;
-    if (c.x_half || c.y_half || c.res_half) {
-        // half views are read / written by the fp16 form of conv_b3d.hip alone
-        if (c.f16 != 1 || !c.wb3r || c.Cin % 16 || op.c.set)
-            return fail(ACCEL_ERR_PLAN, "conv %s: half views need an f16-mode layer with Cin %% 16 == 0, more than 4 output channels and a "
-                                        "single output (plan option dtype=f16, ACCEL_WITHHOLD without b3r)", op.name.c_str());
-    }
-    if ((size_t)op.a.N * op.a.img() * 4 > 0xFFFFFFF0ull || (size_t)op.b.N * op.b.img() * 4 > 0xFFFFFFF0ull)
-        return fail(ACCEL_ERR_PLAN, "conv %s: a batched view exceeds the 4 GiB a buffer resource can address", op.name.c_str());
-    c.x_bytes = extent(op.a, c.Cin > op.a.Cs ? op.a.Cs : c.Cin);
-    c.y_bytes = extent(op.b, cout_store);
-    if (op.c.set) c.y2_bytes = extent(op.c, cout_store);
-    if (op.d.set) c.res_bytes = extent(op.d, cout_store);
+    conv_views(op);
     c.act = (int)kv_int(kv, "act", 0);
     c.slope = (float)kv_f(kv, "slope", 0.1);
-    c.w_bytes = (unsigned)((size_t)rows * c.K_pad * (c.f16 ? 2 : 4));     // of one plane / class
-    {
-        // tap table, one entry per 4-wide K granule: (dy, dx, input byte offset relative to tap 0 / channel 0).
-        // FAST shapes read it wave-uniformly through the scalar unit, the others per lane; padded K and the
-        // slack entries (the pipelined kernels prefetch up to two K steps past the end) are marked out of range.
-        const int G = c.K_pad / 4, classes = c.deconv2x ? 4 : 1, slack = 48;
-        std::vector<int> tab((size_t)classes * (G + slack) * 4, 0);
-        for (int cls = 0; cls < classes; ++cls)
-            for (int g = 0; g < G + slack; ++g) {
-                const int k = g * 4, tap = k / c.Cin, ci = k % c.Cin;
-                const int ky = tap / c.kw, kx = tap % c.kw;
-                int* t = &tab[((size_t)cls * (G + slack) + g) * 4];
-                if (g >= G || tap >= c.kh * c.kw) { t[0] = -(1 << 28); continue; }
-                t[0] = ky * c.dh; t[1] = kx * c.dw;
-                t[2] = ((ky * c.dh * c.W + kx * c.dw) * c.xCs + ci) * op.a.esize;
-            }
-        void* dt = nullptr;
-        if ((rc = dev_upload(p, tab.data(), tab.size() * sizeof(int), &dt))) return rc;
-        c.ktab = static_cast<const int4*>(dt);
-    }
     c.force_tile = (int)kv_int(kv, "tile", -1);
-    if (c.force_tile >= 0 && !conv_tile_valid(c.force_tile))
-        return fail(ACCEL_ERR_ARG, "conv %s: launch geometry id %d is not part of this build", op.name.c_str(), c.force_tile);
-    const int forced_w = c.force_tile >= 0 ? conv_tile(c.force_tile)->weights : -1;      // the weight copy a forced id reads
-    {
-        // Winograd F(2x2,3x3) form of the layer (3x3 / stride 1 / dilation 1 / pad 1): weights transformed here, in
-        // double, once; offered to the autotuner beside the direct tiles (ACCEL_WITHHOLD=winograd withholds it)
-        const bool want = !withheld("winograd") || forced_w == CONV_W_WU;
-        c.M = op.a.N * c.Ho * c.Wo;
-        if (want && !cols && cin == cin_pad && conv_wino_eligible(c)) {
-            c.wino_rows = conv_wino_rows(cout_store);
-            std::vector<float> wu((size_t)(cin_pad / 8) * 16 * c.wino_rows * 8, 0.f);
-            conv_wino_pack(w->data.data(), cout, cin, cin_pad, c.wino_rows, wu.data());
-            void* du = nullptr;
-            if ((rc = dev_upload(p, wu.data(), wu.size() * sizeof(float), &du))) return rc;
-            c.wu = static_cast<const float*>(du);
-            c.wu_bytes = (unsigned)(wu.size() * sizeof(float));
-            // accuracy budget: Winograd evaluations carry about 3x the rounding error of a direct one, and the plan decides which
-            // layers may take the split form (conv key wb3=0 withholds it)
-            const bool wb3_ok = kv_int(kv, "wb3", 1) != 0;
-            const bool wb3_forced = forced_w == CONV_W_WUB;
-            if (((!withheld("split") && !withheld("winograd_split") && wb3_ok) || wb3_forced) && !c.f16 && conv_wino_b3_eligible(c)) {
-                // the same transformed weights as three exact bf16 planes in MFMA fragment order: launch geometry 41
-                std::vector<unsigned short> ub;
-                conv_wino_b3_pack(w->data.data(), cout, cin, c.wino_rows, ub);
-                void* db = nullptr;
-                if ((rc = dev_upload(p, ub.data(), ub.size() * sizeof(unsigned short), &db))) return rc;
-                c.wub = db;
-                c.wub_bytes = (unsigned)(ub.size() * sizeof(unsigned short));
-                if (c.wh2r) {      // fp16x2 form of the layer: the same planes as two half terms
-                    std::vector<int> q;
-                    conv_wino_b3_pack_h2(w->data.data(), cout, cin, c.wino_rows, ub, q);
-                    void *dh = nullptr, *dsh = nullptr;
-                    if ((rc = dev_upload(p, ub.data(), ub.size() * sizeof(unsigned short), &dh))) return rc;
-                    std::vector<float> sh(rows, 0.f);
-                    for (int i = 0; i < rows && i < c.wino_rows; ++i) sh[i] = std::ldexp(scale[i], 2 - q[i]);      // x 4: V is split at a quarter of the pixel scale
-                    if ((rc = dev_upload(p, sh.data(), rows * sizeof(float), &dsh))) return rc;
-                    c.wubh = dh;
-                    c.scale_h2w = static_cast<const float*>(dsh);
-                }
-            }
-        } else if (forced_w == CONV_W_WU || forced_w == CONV_W_WUB) {
+    return 0;
+}
+
+// Step 2: the generic weight copies -- w (fp32, half or the bf16x3 planes, by the layer's mode), wb3 / wb3r (fp32 layers: the bf16x3
+// planes in both orders; f16-mode layers: wb3r is the half plane in fragment order) and wh2r (the fp16x2 planes)
+static int conv_weights(accel_plan* p, Op& op, ConvLayer& L)
+{
+    ConvParams& c = op.conv;
+    const HostParam& w = *L.w;
+    const int rows = L.rows, classes = L.classes;
+    int rc;
+    if (c.deconv2x) pack_deconv2x_w(w.data.data(), L.cin, L.cout, L.cin_pad, rows, c.K_pad, L.packed);
+    else pack_conv_w(w.data.data(), L.cout, L.cin, (int)w.shape[2], (int)w.shape[3], L.cin_pad, rows, c.K_pad, L.packed);
+    L.packed.resize(L.packed.size() + 256, 0.f);   // slack: the pipelined kernel prefetches up to two K steps past the end
+    // fp32 layers also get their weights as three bf16 planes: the bf16x3 kernel (conv_igemm.hip) is then one more launch geometry
+    // (family b3) of the SAME fp32 convolution for the autotuner (ACCEL_WITHHOLD=split withholds it), and the fragment-ordered copy
+    // serves the second-generation kernel (conv_b3r.hip; ACCEL_WITHHOLD=b3r).  A forced id that reads one of these copies gets it
+    // made (asked of the table's row: finalize_conv checks the id against this build)
+    const ConvTile* ft = conv_tile_row(c.force_tile);
+    const bool forced_r = ft && (ft->weights == CONV_W_WB3R || ft->weights == CONV_W_WH2R);
+    const bool forced = forced_r || (ft && ft->weights == CONV_W_WB3);
+    const bool planes = !c.f16 && c.Cin % 4 == 0 && L.cout_store > 4 && (!withheld("split") || forced);
+    const bool frag = c.f16 == 1 ? !withheld("b3r") : planes && (!withheld("b3r") || forced_r);
+    if (c.f16 == 2 || planes || frag) c.w_plane = conv_plane_elems(classes, rows, c.K_pad);
+    std::vector<uint16_t> pb;
+    if (c.f16 == 2) {
+        pack_bf16x3(L.packed, classes, rows, c.K_pad, CONV_ORDER_STEP, pb);
+        if ((rc = upload(p, pb, c.w))) return rc;
+    } else if (c.f16) {
+        std::vector<_Float16> ph(L.packed.size()), pr;
+        for (size_t i = 0; i < L.packed.size(); ++i) ph[i] = (_Float16)L.packed[i];
+        if ((rc = upload(p, ph, c.w))) return rc;
+        if (frag) {      // the fp16 form of conv_b3r.hip (launch geometries 76 / 77 / 79 / 80 / 81 of an f16 layer) and conv_b3d.hip
+            pack_f16r(ph, classes, rows, c.K_pad, pr);
+            if ((rc = upload(p, pr, c.wb3r))) return rc;
+        }
+    } else if ((rc = upload(p, L.packed, c.w))) return rc;
+    if (planes) {
+        pack_bf16x3(L.packed, classes, rows, c.K_pad, CONV_ORDER_STEP, pb);
+        if ((rc = upload(p, pb, c.wb3))) return rc;
+        if (frag) {
+            pack_bf16x3(L.packed, classes, rows, c.K_pad, CONV_ORDER_FRAG, pb);
+            if ((rc = upload(p, pb, c.wb3r))) return rc;
+        }
+    } else if (forced && !(c.f16 == 1 && c.wb3r && forced_r && !(ft->flags & CONV_T_DIAG))) {
+        return fail(ACCEL_ERR_ARG, "conv %s: the bf16x3 kernel takes layers with more than "
+                                   "4 output channels only", op.name.c_str());
+    }
+    const char* sp = getenv("ACCEL_SPLIT");
+    if (c.wb3r && !c.f16 && (sp ? !strcmp(sp, "h2") : p->split == 1)) {
+        pack_h2r(L.packed, classes, rows, c.K_pad, pb, L.q);
+        if ((rc = upload(p, pb, c.wh2r))) return rc;
+        ++p->n_h2;      // (the layer's input range slot, ConvParams::xr_slot, is assigned once every op is known: assign_range_slots)
+    }
+    return 0;
+}
+
+// the epilogue scale of an fp16x2 form: the first n entries of the layer's scale times 2^(k - q[i]) (conv_pack.h conv_h2_scale)
+static int upload_h2_scale(accel_plan* p, const ConvLayer& L, const std::vector<int>& q, int n, int k, const float*& field)
+{
+    std::vector<float> sh;
+    conv_h2_scale(L.scale, q, n, k, sh);
+    return upload(p, sh, field);
+}
+
+// Step 3: the epilogue vectors -- scale / shift (BatchNorm, bias and mul folded), scale_h2 beside wh2r, scale2 / shift2 of an out2
+static int conv_epilogue(accel_plan* p, Op& op, ConvLayer& L)
+{
+    accel_model* m = p->m;
+    const KV& kv = op.kv;
+    ConvParams& c = op.conv;
+    int rc;
+    std::vector<float> s, b, shift;
+    const HostParam* bias = nullptr;
+    const bool bn = kv_has(kv, "bn");
+    if (bn && (rc = bn_fold(m, kv_str(kv, "bn"), (float)kv_f(kv, "eps", 1e-5), (int)kv_int(kv, "fixg", 0), L.cout, s, b))) return rc;
+    if (kv_has(kv, "bias") && (rc = param_n(m, kv_str(kv, "bias"), L.cout, bias))) return rc;
+    const float mul = (float)kv_f(kv, "mul", 1.0);
+    conv_fold_epilogue(L.rows, L.cout, bn ? &s : nullptr, bn ? &b : nullptr, bias ? bias->data.data() : nullptr,
+                       kv_has(kv, "mul") ? &mul : nullptr, L.scale, shift);
+    if ((rc = upload(p, L.scale, c.scale)) || (rc = upload(p, shift, c.shift))) return rc;
+    if (c.wh2r && (rc = upload_h2_scale(p, L, L.q, L.rows, 0, c.scale_h2))) return rc;
+    if (op.c.set) {
+        std::vector<float> s2, b2;
+        const HostParam* bias2 = nullptr;
+        if (kv_has(kv, "bias2")) {          // out2 = relu(v + bias2): the biased, activated copy beside a raw linear output
+            if ((rc = param_n(m, kv_str(kv, "bias2"), L.cout, bias2))) return rc;
+        } else {
+            if (!kv_has(kv, "bn2")) return fail(ACCEL_ERR_PLAN, "conv %s: out2 needs bn2 or bias2", op.name.c_str());
+            if ((rc = bn_fold(m, kv_str(kv, "bn2"), (float)kv_f(kv, "eps2", 2e-5), (int)kv_int(kv, "fixg2", 0), L.cout, s, b))) return rc;
+        }
+        conv_fold_epilogue2(L.rows, L.cout, bias2 ? bias2->data.data() : nullptr, &s, &b, s2, b2);
+        if ((rc = upload(p, s2, c.scale2)) || (rc = upload(p, b2, c.shift2))) return rc;
+    }
+    return 0;
+}
+
+// what the views have to meet, once the layer's weight copies are known
+static int conv_check_views(const Op& op)
+{
+    const ConvParams& c = op.conv;
+    if (op.b.N != op.a.N || (op.c.set && op.c.N != op.a.N) || (op.d.set && op.d.N != op.a.N))
+        return fail(ACCEL_ERR_PLAN, "conv %s: batch sizes of the views differ", op.name.c_str());
+    // half views are read / written by the fp16 form of conv_b3d.hip alone
+    if ((c.x_half || c.y_half || c.res_half) && (c.f16 != 1 || !c.wb3r || c.Cin % 16 || op.c.set))
+        return fail(ACCEL_ERR_PLAN, "conv %s: half views need an f16-mode layer with Cin %% 16 == 0, more than 4 output channels and a "
+                                    "single output (plan option dtype=f16, ACCEL_WITHHOLD without b3r)", op.name.c_str());
+    if ((size_t)op.a.N * op.a.img() * 4 > 0xFFFFFFF0ull || (size_t)op.b.N * op.b.img() * 4 > 0xFFFFFFF0ull)
+        return fail(ACCEL_ERR_PLAN, "conv %s: a batched view exceeds the 4 GiB a buffer resource can address", op.name.c_str());
+    return 0;
+}
+
+// Step 5, one function per family form: its want / forced / eligible logic, its copies and its refusal.
+// Winograd F(2x2,3x3) form of the layer (3x3 / stride 1 / dilation 1 / pad 1): weights transformed here, in double, once; offered to
+// the autotuner beside the direct tiles (ACCEL_WITHHOLD=winograd withholds it)
+static int conv_form_wino(accel_plan* p, Op& op, const ConvLayer& L)
+{
+    const KV& kv = op.kv;
+    ConvParams& c = op.conv;
+    const float* w = L.w->data.data();
+    int rc;
+    const bool want = !withheld("winograd") || L.forced_w == CONV_W_WU;
+    if (!(want && !L.cols && L.cin == L.cin_pad && conv_wino_eligible(c))) {
+        if (L.forced_w == CONV_W_WU || L.forced_w == CONV_W_WUB)
             return fail(ACCEL_ERR_ARG, "conv %s: the Winograd kernel takes 3x3 / stride 1 / dilation 1 / pad 1 layers with even output "
                                        "size and channels in multiples of 8 only", op.name.c_str());
-        }
+        return 0;
     }
-    {
-        // direct stem kernel (7x7 / stride 2 / pad 3, 3-channel image, 64 output channels): per-lane weight arrangement
-        const bool want = !withheld("stem") || forced_w == CONV_W_WSTEM || forced_w == CONV_W_WSTEMB;
-        c.Cout_store = cout_store;
-        c.res = op.d.set ? op.d.ptr : nullptr;
-        if (want && !cols && cin == 3 && cout == 64 && conv_stem_eligible(c)) {
-            std::vector<float> ws((size_t)conv_stem_pack_floats(), 0.f);
-            conv_stem_pack(w->data.data(), cout, ws.data());
-            void* dsw = nullptr;
-            if ((rc = dev_upload(p, ws.data(), ws.size() * sizeof(float), &dsw))) return rc;
-            c.wstem = static_cast<const float*>(dsw);
-            if ((!withheld("split") && !withheld("stem_split")) || forced_w == CONV_W_WSTEMB) {
-                // the same layer for the bf16 matrix cores: three exact bf16 planes in MFMA fragment order (launch geometry 51)
-                std::vector<unsigned short> wb;
-                conv_stem_b3_pack(w->data.data(), cout, wb);
-                void* dsb = nullptr;
-                if ((rc = dev_upload(p, wb.data(), wb.size() * sizeof(unsigned short), &dsb))) return rc;
-                c.wstemb = dsb;
-                if (c.wh2r) {      // fp16x2 form of the layer
-                    std::vector<int> q;
-                    conv_stem_b3_pack_h2(w->data.data(), cout, wb, q);
-                    void *dh = nullptr, *dsh = nullptr;
-                    if ((rc = dev_upload(p, wb.data(), wb.size() * sizeof(unsigned short), &dh))) return rc;
-                    std::vector<float> sh(rows, 0.f);
-                    for (int i = 0; i < rows && i < 64; ++i) sh[i] = std::ldexp(scale[i], -q[i]);
-                    if ((rc = dev_upload(p, sh.data(), rows * sizeof(float), &dsh))) return rc;
-                    c.wstemh = dh;
-                    c.scale_h2s = static_cast<const float*>(dsh);
-                }
-            }
-        } else if (forced_w == CONV_W_WSTEM || forced_w == CONV_W_WSTEMB) {
+    c.wino_rows = conv_wino_rows(L.cout_store);
+    std::vector<float> wu((size_t)(L.cin_pad / 8) * 16 * c.wino_rows * 8, 0.f);
+    conv_wino_pack(w, L.cout, L.cin, L.cin_pad, c.wino_rows, wu.data());
+    if ((rc = upload(p, wu, c.wu))) return rc;
+    c.wu_bytes = (unsigned)(wu.size() * sizeof(float));
+    // accuracy budget: Winograd evaluations carry about 3x the rounding error of a direct one, and the plan decides which
+    // layers may take the split form (conv key wb3=0 withholds it)
+    const bool wb3_ok = kv_int(kv, "wb3", 1) != 0;
+    const bool wb3_forced = L.forced_w == CONV_W_WUB;
+    if (!(((!withheld("split") && !withheld("winograd_split") && wb3_ok) || wb3_forced) && !c.f16 && conv_wino_b3_eligible(c))) return 0;
+    // the same transformed weights as three exact bf16 planes in MFMA fragment order: launch geometry 41
+    std::vector<unsigned short> ub;
+    conv_wino_b3_pack(w, L.cout, L.cin, c.wino_rows, ub);
+    if ((rc = upload(p, ub, c.wub))) return rc;
+    c.wub_bytes = (unsigned)(ub.size() * sizeof(unsigned short));
+    if (c.wh2r) {      // fp16x2 form of the layer: the same planes as two half terms
+        std::vector<int> q;
+        conv_wino_b3_pack_h2(w, L.cout, L.cin, c.wino_rows, ub, q);
+        if ((rc = upload(p, ub, c.wubh)) ||
+            (rc = upload_h2_scale(p, L, q, c.wino_rows, 2, c.scale_h2w))) return rc;      // x 4: V is split at a quarter of the pixel scale
+    }
+    return 0;
+}
+
+// direct stem kernel (7x7 / stride 2 / pad 3, 3-channel image, 64 output channels): per-lane weight arrangement
+static int conv_form_stem(accel_plan* p, Op& op, const ConvLayer& L)
+{
+    ConvParams& c = op.conv;
+    const float* w = L.w->data.data();
+    int rc;
+    const bool want = !withheld("stem") || L.forced_w == CONV_W_WSTEM || L.forced_w == CONV_W_WSTEMB;
+    if (!(want && !L.cols && L.cin == 3 && L.cout == 64 && conv_stem_eligible(c))) {
+        if (L.forced_w == CONV_W_WSTEM || L.forced_w == CONV_W_WSTEMB)
             return fail(ACCEL_ERR_ARG, "conv %s: the stem kernel takes 7x7 / stride 2 / pad 3 layers on 3-channel images with 64 "
                                        "output channels only", op.name.c_str());
-        }
+        return 0;
     }
-    {
-        // weight-stationary streaming kernel for the 1x1 expand layers with K = 64 / 128 (ACCEL_WITHHOLD=ws1x1 withholds it)
-        const bool want = !withheld("ws1x1") || forced_w == CONV_W_WWS;
-        c.y2 = op.c.set ? op.c.ptr : nullptr;
-        if (want && !cols && cin == cin_pad && conv_ws_eligible(c)) {
-            std::vector<float> ww(conv_ws_pack_floats(cin, cout_store), 0.f);
-            conv_ws_pack(w->data.data(), cout, cin, cout_store, ww.data());
-            void* dw = nullptr;
-            if ((rc = dev_upload(p, ww.data(), ww.size() * sizeof(float), &dw))) return rc;
-            c.wws = static_cast<const float*>(dw);
-            c.wws_bytes = (unsigned)(ww.size() * sizeof(float));
-        } else if (forced_w == CONV_W_WWS) {
+    std::vector<float> ws((size_t)conv_stem_pack_floats(), 0.f);
+    conv_stem_pack(w, L.cout, ws.data());
+    if ((rc = upload(p, ws, c.wstem))) return rc;
+    if (!((!withheld("split") && !withheld("stem_split")) || L.forced_w == CONV_W_WSTEMB)) return 0;
+    // the same layer for the bf16 matrix cores: three exact bf16 planes in MFMA fragment order (launch geometry 51)
+    std::vector<unsigned short> wb;
+    conv_stem_b3_pack(w, L.cout, wb);
+    if ((rc = upload(p, wb, c.wstemb))) return rc;
+    if (c.wh2r) {      // fp16x2 form of the layer
+        std::vector<int> q;
+        conv_stem_b3_pack_h2(w, L.cout, wb, q);
+        if ((rc = upload(p, wb, c.wstemh)) || (rc = upload_h2_scale(p, L, q, 64, 0, c.scale_h2s))) return rc;
+    }
+    return 0;
+}
+
+// weight-stationary streaming kernel for the 1x1 expand layers with K = 64 / 128 (ACCEL_WITHHOLD=ws1x1 withholds it)
+static int conv_form_ws(accel_plan* p, Op& op, const ConvLayer& L)
+{
+    ConvParams& c = op.conv;
+    const bool want = !withheld("ws1x1") || L.forced_w == CONV_W_WWS;
+    if (!(want && !L.cols && L.cin == L.cin_pad && conv_ws_eligible(c))) {
+        if (L.forced_w == CONV_W_WWS)
             return fail(ACCEL_ERR_ARG, "conv %s: the weight-stationary kernel takes 1x1 / stride 1 layers from 64 to a multiple of 256 "
                                        "or from 128 to a multiple of 128 channels (ReLU or no activation, one output) only", op.name.c_str());
-        }
+        return 0;
     }
-    c.narrow = (cout_store == 4 && !c.deconv2x && !op.c.set && c.force_tile < 0 && kv_int(kv, "narrow", 1)) ? 1 : 0;
+    std::vector<float> ww(conv_ws_pack_floats(L.cin, L.cout_store), 0.f);
+    conv_ws_pack(L.w->data.data(), L.cout, L.cin, L.cout_store, ww.data());
+    if (int rc = upload(p, ww, c.wws)) return rc;
+    c.wws_bytes = (unsigned)(ww.size() * sizeof(float));
+    return 0;
+}
+
+static int finalize_conv(accel_plan* p, Op& op)
+{
+    const KV& kv = op.kv;
+    ConvParams& c = op.conv;
+    ConvLayer L;
+    int rc;
+    if ((rc = conv_geometry(p, op, L)) || (rc = conv_weights(p, op, L)) || (rc = conv_epilogue(p, op, L)) ||
+        (rc = conv_check_views(op))) return rc;
+    {
+        // Step 4: the tap table (conv_pack.h)
+        std::vector<int> tab;
+        conv_tap_table(L.classes, c.K_pad, c.Cin, c.kh, c.kw, c.dh, c.dw, c.W, c.xCs, op.a.esize, tab);
+        if ((rc = upload(p, tab, c.ktab))) return rc;
+    }
+    if (c.force_tile >= 0 && !conv_tile_valid(c.force_tile))
+        return fail(ACCEL_ERR_ARG, "conv %s: launch geometry id %d is not part of this build", op.name.c_str(), c.force_tile);
+    L.forced_w = c.force_tile >= 0 ? conv_tile(c.force_tile)->weights : -1;
+    // The family forms.  An *_eligible function may read what conv_geometry filled -- the shape (H, W, Cin, Ho, Wo, kh .. dw, K_pad,
+    // deconv2x, yH, yW), M, Cout, Cout_store, the views with their strides, half flags and extents (x, y, y2, res; null: no such
+    // view), act, slope, f16 and force_tile -- and, of what the steps before this one made, whether a generic copy exists (w, wb3,
+    // wb3r, wh2r) and ktab.  It may NOT read what is decided after the forms: narrow, no_split, split_target, ksplit (all still 0).
+    if ((rc = conv_form_wino(p, op, L)) || (rc = conv_form_stem(p, op, L)) || (rc = conv_form_ws(p, op, L))) return rc;
+    // Step 6: the split plan
+    c.narrow = (L.cout_store == 4 && !c.deconv2x && !op.c.set && c.force_tile < 0 && kv_int(kv, "narrow", 1)) ? 1 : 0;
     c.no_split = (int)kv_int(kv, "nosplit", 0);
     c.split_target = (int)kv_int(kv, "split_target", 0);      // (tests: the tuner's "split until ~N blocks" variants, forced)
     const size_t ws = conv_plan_split(c);
@@ -795,14 +704,9 @@ static int finalize_conv(accel_plan* p, Op& op)
 
 static int upload_param(accel_plan* p, const std::string& name, size_t expect, const float** out)
 {
-    const HostParam* h = get_param(p->m, name);
-    if (!h) return fail(ACCEL_ERR_PARAM, "%s not initialized", name.c_str());
-    if (expect && h->numel() != expect) return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s: %zu elements, expected %zu", name.c_str(), h->numel(), expect);
-    void* d = nullptr;
-    int rc = dev_upload(p, h->data.data(), h->numel() * sizeof(float), &d);
-    if (rc) return rc;
-    *out = static_cast<const float*>(d);
-    return 0;
+    const HostParam* h;
+    if (int rc = param_n(p->m, name, expect, h, true)) return rc;
+    return upload(p, h->data, *out);
 }
 
 // the pointer slot of a whole persistent input buffer read by a prep kernel (null for arena views and partial views)
@@ -873,9 +777,7 @@ static int finalize_op(accel_plan* p, Op& op)
         if (kv_has(kv, "bn")) {
             std::vector<float> s, b;
             if ((rc = bn_fold(p->m, kv_str(kv, "bn"), (float)kv_f(kv, "eps", 2e-5), (int)kv_int(kv, "fixg", 1), 3, s, b))) return rc;
-            void *ds = nullptr, *db = nullptr;
-            if ((rc = dev_upload(p, s.data(), 12, &ds)) || (rc = dev_upload(p, b.data(), 12, &db))) return rc;
-            op.p0 = static_cast<const float*>(ds); op.p1 = static_cast<const float*>(db);
+            if ((rc = upload(p, s, op.p0)) || (rc = upload(p, b, op.p1))) return rc;
         }
         return 0;
     }
@@ -906,9 +808,7 @@ static int finalize_op(accel_plan* p, Op& op)
             std::vector<float> s, b;
             if ((rc = bn_fold(p->m, kv_str(kv, "bn"), (float)kv_f(kv, "eps", 2e-5), (int)kv_int(kv, "fixg", 0), op.a.C, s, b))) return rc;
             s.resize(q.C4 * 4, 0.f); b.resize(q.C4 * 4, 0.f);
-            void *ds = nullptr, *db = nullptr;
-            if ((rc = dev_upload(p, s.data(), s.size() * 4, &ds)) || (rc = dev_upload(p, b.data(), b.size() * 4, &db))) return rc;
-            q.scale = static_cast<const float*>(ds); q.shift = static_cast<const float*>(db);
+            if ((rc = upload(p, s, q.scale)) || (rc = upload(p, b, q.shift))) return rc;
         }
         return 0;
     }
@@ -918,12 +818,8 @@ static int finalize_op(accel_plan* p, Op& op)
         if (op.a.C % 4) return fail(ACCEL_ERR_PLAN, "warp: C must be a multiple of 4");
         if (kv_has(kv, "out2")) {           // second output relu(warped + bias[c])
             if ((rc = parse_buf(kv, "out2", op.d)) || (rc = resolve(p, op.d, "out2"))) return rc;
-            const HostParam* bias = get_param(p->m, kv_str(kv, "bias"));
-            if (!bias) return fail(ACCEL_ERR_PARAM, "%s not initialized", kv_str(kv, "bias").c_str());
-            if ((int)bias->numel() != op.a.C) return fail(ACCEL_ERR_PARAM, "shape inconsistent for %s", kv_str(kv, "bias").c_str());
-            void* db = nullptr;
-            if ((rc = dev_upload(p, bias->data.data(), (size_t)op.a.C * sizeof(float), &db))) return rc;
-            op.p0 = static_cast<const float*>(db);
+            const HostParam* bias;
+            if ((rc = param_n(p->m, kv_str(kv, "bias"), op.a.C, bias)) || (rc = upload(p, bias->data, op.p0))) return rc;
         }
         return 0;
     }

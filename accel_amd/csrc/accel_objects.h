@@ -1,4 +1,4 @@
-// libaccel_hip, internal: what its translation units share -- accel_hip.cpp (plans: parser, packers, tuner, executor) and accel_io.cpp (bytes in and
+// libaccel_hip, internal: what its translation units share -- accel_hip.cpp (plans: parser, tuner, executor) and accel_io.cpp (bytes in and
 // out of a model's persistent buffers, frames and results).  Everything about plans stays private to accel_hip.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
