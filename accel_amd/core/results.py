@@ -4,7 +4,7 @@ _labels_colour / _hist_add / _hist_read) -- and the logits themselves finished a
 accel_model_confidence), or as labels of their own: `interpolate=True` takes the LOGITS handle, interpolates the scores bilinearly to the
 source size and takes the argmax there (csrc/scores_labels.hip behind accel_model_scores_labels / _scores_hist_add / _scores_colour), and
 `confidence(..., interpolate=True)` takes the confidence from those interpolated scores too, with the labels if asked, in one pass
-(csrc/scores_confidence.hip behind accel_model_confidence_interp).  `overlay` blends the labels over NV12 / I420 / P010 / YUY2 frames and
+(the interpolated form of csrc/confidence.hip behind accel_model_confidence_interp).  `overlay` blends the labels over NV12 / I420 / P010 / YUY2 frames and
 hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).  `summary` says what
 is in the frame, where, and whether it just changed: per-class areas, coordinate sums and boxes, and the class transitions against the
 previous frame, which is kept in HBM (csrc/labels_summary.hip behind accel_model_labels_summary / _scores_summary / _labels_forget).

@@ -601,6 +601,15 @@ static int results_args(const char* fn, int n, int H, int W, int out_h, int out_
     return 0;
 }
 
+// the same for the entry points that interpolate the scores (scores_labels.hip): the class count first
+static int scores_labels_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w)
+{
+    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the scores must have 2, 19 or 21 classes", fn, ncls);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    return 0;
+}
+
 static int pitch_arg(const char* fn, const char* name, size_t pitch, int w, int bytes_per_pixel)
 {
     if (pitch < (size_t)bytes_per_pixel * w)
@@ -723,6 +732,54 @@ static int model_scores(const char* fn, accel_model* m, int n, const float** sco
     return 0;
 }
 
+// Where the label maps of a model-level result come from, in one of two kinds:
+//   NEAREST        the `labels` buffer the plans write -- n maps of H x W whose valid region out_h x out_w the consumer takes to the source size by
+//                  the nearest rule: the consumer's geometry is the map's own H, W, out_h, out_w
+//   INTERPOLATED   the argmax of the `logits` interpolated to the source size h x w (launch_scores_labels), which enqueue() writes into the model's
+//                  scratch as tight rows: the consumer's geometry is the identity h, w, h, w
+// An entry point uses it in this order: find (the buffer, n against the bound batch), geometry (INTERPOLATED: the class count of the scores first),
+// its own checks, reserve (the scratch), and enqueue in front of the consumer's kernel -- or write alone, for the labels themselves.
+struct LabelSource {
+    enum Kind { NEAREST, INTERPOLATED };
+    accel_model* m;
+    Kind kind;
+    const unsigned char* maps = nullptr;            // what the consumer reads (INTERPOLATED: from reserve() on) ...
+    int n = 0, H = 0, W = 0, out_h = 0, out_w = 0, h = 0, w = 0;       // ... and the geometry it reads it in
+    const float* scores = nullptr;                  // INTERPOLATED: the logits
+    int ncls = 0, bH = 0, bW = 0, b_out_h = 0, b_out_w = 0;            // the buffer's own shape and valid region
+
+    LabelSource(accel_model* m_, Kind kind_) : m(m_), kind(kind_) {}
+
+    int find(const char* fn, int n_)
+    {
+        n = n_;
+        if (kind == INTERPOLATED) return model_scores(fn, m, n, &scores, &ncls, &bH, &bW);
+        bH = m->labels_h; bW = m->labels_w;
+        return model_labels(fn, m, n, &maps);
+    }
+    int geometry(const char* fn, int out_h_, int out_w_, int h_, int w_)
+    {
+        b_out_h = out_h_; b_out_w = out_w_; h = h_; w = w_;
+        const bool own = kind == NEAREST;
+        H = own ? bH : h; W = own ? bW : w; out_h = own ? out_h_ : h; out_w = own ? out_w_ : w;
+        return own ? results_args(fn, n, bH, bW, out_h_, out_w_, h, w) : scores_labels_args(fn, n, ncls, bH, bW, out_h_, out_w_, h, w);
+    }
+    int reserve()
+    {
+        if (kind == NEAREST) return 0;
+        if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
+        maps = m->interp_labels.ptr;
+        return 0;
+    }
+    // the labels at the source size straight into `dst`
+    hipError_t write(unsigned char* dst, size_t pitch, hipStream_t st) const
+    {
+        if (kind == NEAREST) return launch_labels_source(maps, n, bH, bW, b_out_h, b_out_w, h, w, dst, pitch, st);
+        return launch_scores_labels(scores, n, ncls, bH, bW, b_out_h, b_out_w, h, w, dst, pitch, st);
+    }
+    hipError_t enqueue(hipStream_t st) const { return kind == NEAREST ? hipSuccess : write(m->interp_labels.ptr, (size_t)w, st); }
+};
+
 // Where the `rows` rows of `row` bytes of a result go.  Into the caller's device memory at the caller's pitch: `launch(dst, pitch, stream)` is enqueued
 // and that is all.  To the host: the kernel writes tight rows into the staging buffer, they are copied `dst_pitch` apart, and the call waits.
 template <class Launch>
@@ -754,39 +811,63 @@ static int model_hist(const char* fn, accel_model* m, int ncls, unsigned long lo
     return 0;
 }
 
-extern "C" int accel_model_labels_to_source(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+// the labels themselves: written straight to the destination (or the staging buffer), never through the scratch
+static int model_labels_out(const char* fn, accel_model* m, LabelSource::Kind kind, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch,
+                            int dst_on_device)
 {
-    const char* fn = "accel_model_labels_to_source";
     if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
     if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
-    const unsigned char* labels = nullptr;
-    if (int rc = model_labels(fn, m, n, &labels)) return rc;
-    const int H = m->labels_h, W = m->labels_w;
-    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
     if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    if (dst_on_device) HIP_TRY(hipSetDevice(m->ctx->device));
     return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
-        return launch_labels_source(labels, n, H, W, out_h, out_w, h, w, d, pitch, st);
+        return src.write(d, pitch, st);
     });
 }
 
-extern "C" int accel_model_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device)
+extern "C" int accel_model_labels_to_source(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
 {
-    const char* fn = "accel_model_hist_add";
+    return model_labels_out("accel_model_labels_to_source", m, LabelSource::NEAREST, n, out_h, out_w, h, w, dst, dst_pitch, dst_on_device);
+}
+
+extern "C" int accel_model_scores_labels(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
+{
+    return model_labels_out("accel_model_scores_labels", m, LabelSource::INTERPOLATED, n, out_h, out_w, h, w, dst, dst_pitch, dst_on_device);
+}
+
+static int model_hist_add(const char* fn, accel_model* m, LabelSource::Kind kind, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h,
+                          int out_w, int ncls, int gt_on_device)
+{
     if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
     if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
-    const unsigned char* labels = nullptr;
-    if (int rc = model_labels(fn, m, n, &labels)) return rc;
-    const int H = m->labels_h, W = m->labels_w;
-    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
     if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
     if (int rc = ncls_arg(fn, ncls)) return rc;
     unsigned long long* hist = nullptr;
     if (int rc = model_hist(fn, m, ncls, &hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (int rc = src.reserve()) return rc;
     const unsigned char* g = gt;
     if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
-    HIP_TRY(launch_labels_hist(labels, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, hist, m->ctx->stream));
+    HIP_TRY(src.enqueue(st));
+    HIP_TRY(launch_labels_hist(src.maps, n, src.H, src.W, src.out_h, src.out_w, g, h, w, gt_pitch, ncls, hist, st));
     m->hist_ncls = ncls;
     return 0;
+}
+
+extern "C" int accel_model_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls, int gt_on_device)
+{
+    return model_hist_add("accel_model_hist_add", m, LabelSource::NEAREST, gt, n, h, w, gt_pitch, out_h, out_w, ncls, gt_on_device);
+}
+
+extern "C" int accel_model_scores_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                           int gt_on_device)
+{
+    return model_hist_add("accel_model_scores_hist_add", m, LabelSource::INTERPOLATED, gt, n, h, w, gt_pitch, out_h, out_w, ncls, gt_on_device);
 }
 
 extern "C" int accel_model_hist_read(accel_model* m, uint64_t* out, int ncls, int clear)
@@ -809,189 +890,179 @@ extern "C" int accel_model_hist_read(accel_model* m, uint64_t* out, int ncls, in
     return 0;
 }
 
+static int model_colour(const char* fn, accel_model* m, LabelSource::Kind kind, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb,
+                        int rgb_order, const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device, uint8_t* dst, size_t dst_pitch,
+                        int dst_on_device)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
+    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
+    if (int rc = alpha_arg(fn, alpha)) return rc;
+    if (int rc = src.reserve()) return rc;
+    const unsigned char* f = frame_bgr;
+    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
+    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)3 * w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
+        const hipError_t e = src.enqueue(st);
+        if (e != hipSuccess) return e;
+        return launch_labels_colour(src.maps, n, src.H, src.W, src.out_h, src.out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);
+    });
+}
+
 extern "C" int accel_model_labels_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
                                          const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
                                          uint8_t* dst, size_t dst_pitch, int dst_on_device)
 {
-    const char* fn = "accel_model_labels_colour";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
-    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
-    const unsigned char* labels = nullptr;
-    if (int rc = model_labels(fn, m, n, &labels)) return rc;
-    const int H = m->labels_h, W = m->labels_w;
-    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
-    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
-    if (int rc = alpha_arg(fn, alpha)) return rc;
-    const unsigned char* f = frame_bgr;
-    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
-    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)3 * w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
-        return launch_labels_colour(labels, n, H, W, out_h, out_w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);
-    });
+    return model_colour("accel_model_labels_colour", m, LabelSource::NEAREST, n, out_h, out_w, h, w, palette_rgb, rgb_order, frame_bgr, frame_pitch, alpha,
+                        frame_on_device, dst, dst_pitch, dst_on_device);
 }
 
-// ---- confidence of finished frames (confidence.hip) ----------------------------------------------------------------------------------------
-// What the two entry points share, checked before anything is enqueued: every message names the argument at fault.
-// (`with_labels`: the entry point has a labels output at all -- the interpolated forms; the others pass false, NULL, 0)
-static int confidence_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, const void* conf, size_t conf_pitch,
-                           const void* margin, size_t margin_pitch, const void* second, size_t second_pitch, const void* hist,
-                           bool with_labels = false, const void* labels = nullptr, size_t labels_pitch = 0)
+extern "C" int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
+                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
+                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
 {
-    if (!labels && !conf && !margin && !second && !hist)
-        return fail(ACCEL_ERR_ARG, "%s: %sconf, margin, second and hist are all NULL: nothing to compute", fn, with_labels ? "labels, " : "");
+    return model_colour("accel_model_scores_colour", m, LabelSource::INTERPOLATED, n, out_h, out_w, h, w, palette_rgb, rgb_order, frame_bgr, frame_pitch, alpha,
+                        frame_on_device, dst, dst_pitch, dst_on_device);
+}
+
+// ---- confidence of finished frames: of the stored scores (nearest) and of the interpolated ones, with their labels (confidence.hip) ---------
+// The outputs of a call are one ConfOut (kernels.h): five pointers and four pitches, on the host or on the device; `labels` exists in the
+// interpolated forms only and is NULL in the nearest ones.
+// What the four entry points share, checked before anything is enqueued: every message names the argument at fault.
+static int confidence_args(const char* fn, bool interp, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, const ConfOut& o)
+{
+    if (!o.labels && !o.conf && !o.margin && !o.second && !o.hist)
+        return fail(ACCEL_ERR_ARG, "%s: %sconf, margin, second and hist are all NULL: nothing to compute", fn, interp ? "labels, " : "");
     if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, must be 2, 19 or 21", fn, ncls);
     if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
     if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
-    if (labels) if (int rc = pitch_arg(fn, "labels_pitch", labels_pitch, w, 1)) return rc;
-    if (conf) if (int rc = pitch_arg(fn, "conf_pitch", conf_pitch, w, 1)) return rc;
-    if (margin) {
-        if (int rc = pitch_arg(fn, "margin_pitch", margin_pitch, w, 4)) return rc;
-        if (margin_pitch % 4) return fail(ACCEL_ERR_ARG, "%s: margin_pitch = %zu bytes, must be a multiple of 4", fn, margin_pitch);
+    if (o.labels) if (int rc = pitch_arg(fn, "labels_pitch", o.labels_pitch, w, 1)) return rc;
+    if (o.conf) if (int rc = pitch_arg(fn, "conf_pitch", o.conf_pitch, w, 1)) return rc;
+    if (o.margin) {
+        if (int rc = pitch_arg(fn, "margin_pitch", o.margin_pitch, w, 4)) return rc;
+        if (o.margin_pitch % 4) return fail(ACCEL_ERR_ARG, "%s: margin_pitch = %zu bytes, must be a multiple of 4", fn, o.margin_pitch);
     }
-    if (second) if (int rc = pitch_arg(fn, "second_pitch", second_pitch, w, 1)) return rc;
+    if (o.second) if (int rc = pitch_arg(fn, "second_pitch", o.second_pitch, w, 1)) return rc;
     return 0;
 }
 
-// the device side of a call whose results go to the host: tight rows in `base` (labels, conf, second: n * h * w bytes; margin: 4 times that; hist:
-// n * 256 words), each part 256-byte aligned
-struct ConfStage {
-    size_t labels = 0, conf = 0, second = 0, margin = 0, hist = 0, bytes = 0;
-    ConfStage(int n, int h, int w, bool c, bool mg, bool s, bool hi, bool lab = false)
+// a staging buffer carved into parts, each 256-byte aligned: take(bytes) -> the offset of the next part
+struct Carved {
+    size_t bytes = 0;
+    size_t take(size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; }
+};
+
+// the device side of a call whose results go to the host: tight rows (labels, conf, second: n * h * w bytes; margin: 4 times that; hist: n * 256
+// words) for the outputs `host` asks for
+struct ConfStage : Carved {
+    size_t labels = 0, conf = 0, second = 0, margin = 0, hist = 0;
+    ConfStage(int n, int h, int w, const ConfOut& host)
     {
         const size_t px = (size_t)n * h * w;
-        auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
-        if (lab) labels = take(px);
-        if (c) conf = take(px);
-        if (s) second = take(px);
-        if (mg) margin = take(px * 4);
-        if (hi) hist = take((size_t)n * 256 * sizeof(uint64_t));
+        if (host.labels) labels = take(px);
+        if (host.conf) conf = take(px);
+        if (host.second) second = take(px);
+        if (host.margin) margin = take(px * 4);
+        if (host.hist) hist = take((size_t)n * 256 * sizeof(uint64_t));
+    }
+    ConfOut at(unsigned char* base, int w, const ConfOut& host) const
+    {
+        return {host.labels ? base + labels : nullptr, (size_t)w, host.conf ? base + conf : nullptr, (size_t)w,
+                host.margin ? reinterpret_cast<float*>(base + margin) : nullptr, (size_t)4 * w, host.second ? base + second : nullptr, (size_t)w,
+                host.hist ? reinterpret_cast<unsigned long long*>(base + hist) : nullptr};
     }
 };
 
-// `interp`: the interpolated form (launch_scores_confidence, which can also hand out `labels`) instead of the nearest one (launch_confidence)
-static int confidence_to_host(const char* fn, const float* scores, unsigned char* base, const ConfStage& cs, int n, int ncls, int H, int W, int out_h, int out_w,
-                              int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second,
-                              size_t second_pitch, uint64_t* hist, hipStream_t st, bool interp = false, uint8_t* labels = nullptr, size_t labels_pitch = 0)
+// the kernel into the stage at `base`, its results copied to the host; the call waits
+static int confidence_to_host(const float* scores, unsigned char* base, const ConfStage& cs, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                              int is_prob, bool interp, const ConfOut& host, hipStream_t st)
 {
-    unsigned char* dl = labels ? base + cs.labels : nullptr;
-    unsigned char* dc = conf ? base + cs.conf : nullptr;
-    unsigned char* ds = second ? base + cs.second : nullptr;
-    float* dm = margin ? reinterpret_cast<float*>(base + cs.margin) : nullptr;
-    unsigned long long* dh = hist ? reinterpret_cast<unsigned long long*>(base + cs.hist) : nullptr;
-    if (interp)
-        HIP_TRY(launch_scores_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dl, (size_t)w, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
-    else
-        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, dc, (size_t)w, dm, (size_t)4 * w, ds, (size_t)w, dh, st));
-    if (labels) HIP_TRY(rows_to_host(labels, labels_pitch, dl, (size_t)w, (size_t)n * h, st));
-    if (conf) HIP_TRY(rows_to_host(conf, conf_pitch, dc, (size_t)w, (size_t)n * h, st));
-    if (second) HIP_TRY(rows_to_host(second, second_pitch, ds, (size_t)w, (size_t)n * h, st));
-    if (margin) HIP_TRY(rows_to_host(margin, margin_pitch, dm, (size_t)4 * w, (size_t)n * h, st));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, dh, (size_t)n * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    const ConfOut d = cs.at(base, w, host);
+    const size_t rows = (size_t)n * h;
+    HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, interp, d, st));
+    if (host.labels) HIP_TRY(rows_to_host(host.labels, host.labels_pitch, d.labels, (size_t)w, rows, st));
+    if (host.conf) HIP_TRY(rows_to_host(host.conf, host.conf_pitch, d.conf, (size_t)w, rows, st));
+    if (host.second) HIP_TRY(rows_to_host(host.second, host.second_pitch, d.second, (size_t)w, rows, st));
+    if (host.margin) HIP_TRY(rows_to_host(host.margin, host.margin_pitch, d.margin, (size_t)4 * w, rows, st));
+    if (host.hist) HIP_TRY(hipMemcpyAsync(host.hist, d.hist, (size_t)n * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+static int ctx_confidence(const char* fn, accel_ctx* ctx, const float* scores, bool interp, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
+                          int is_prob, const ConfOut& o)
+{
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
+    if (int rc = confidence_args(fn, interp, n, ncls, H, W, out_h, out_w, h, w, o)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const ConfStage cs(n, h, w, o);
+    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    return confidence_to_host(s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, interp, o, ctx->stream);
+}
+
+static int model_confidence(const char* fn, accel_model* m, bool interp, int n, int out_h, int out_w, int h, int w, int is_prob, const ConfOut& o,
+                            int dst_on_device)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    const float* scores = nullptr;
+    int ncls = 0, H = 0, W = 0;
+    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
+    if (int rc = confidence_args(fn, interp, n, ncls, H, W, out_h, out_w, h, w, o)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(o.margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)o.margin);
+        if (reinterpret_cast<uintptr_t>(o.hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)o.hist);
+        HIP_TRY(hipSetDevice(m->ctx->device));
+        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, interp, o, st));
+        return 0;
+    }
+    const ConfStage cs(n, h, w, o);
+    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
+    return confidence_to_host(scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, interp, o, st);
 }
 
 extern "C" int accel_scores_confidence(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
                                        uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
                                        uint64_t* hist)
 {
-    const char* fn = "accel_scores_confidence";
-    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
-    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
-    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevTemps t;
-    const ConfStage cs(n, h, w, conf, margin, second, hist);
-    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
-    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
-    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    return confidence_to_host(fn, s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
-                              hist, ctx->stream);
+    return ctx_confidence("accel_scores_confidence", ctx, scores, false, n, ncls, H, W, out_h, out_w, h, w, is_prob,
+                          {nullptr, 0, conf, conf_pitch, margin, margin_pitch, second, second_pitch, reinterpret_cast<unsigned long long*>(hist)});
 }
 
 extern "C" int accel_model_confidence(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* conf, size_t conf_pitch,
                                       float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist, int dst_on_device)
 {
-    const char* fn = "accel_model_confidence";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const float* scores = nullptr;
-    int ncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
-    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist)) return rc;
-    hipStream_t st = m->ctx->stream;
-    if (dst_on_device) {
-        if (reinterpret_cast<uintptr_t>(margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)margin);
-        if (reinterpret_cast<uintptr_t>(hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)hist);
-        HIP_TRY(hipSetDevice(m->ctx->device));
-        HIP_TRY(launch_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
-                                  reinterpret_cast<unsigned long long*>(hist), st));
-        return 0;
-    }
-    const ConfStage cs(n, h, w, conf, margin, second, hist);
-    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
-    return confidence_to_host(fn, scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second,
-                              second_pitch, hist, st);
+    return model_confidence("accel_model_confidence", m, false, n, out_h, out_w, h, w, is_prob,
+                            {nullptr, 0, conf, conf_pitch, margin, margin_pitch, second, second_pitch, reinterpret_cast<unsigned long long*>(hist)},
+                            dst_on_device);
 }
 
-// ---- confidence of interpolated scores, with their labels (scores_confidence.hip) ------------------------------------------------------------------
 extern "C" int accel_scores_confidence_interp(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
                                               int is_prob, uint8_t* labels, size_t labels_pitch, uint8_t* conf, size_t conf_pitch, float* margin,
                                               size_t margin_pitch, uint8_t* second, size_t second_pitch, uint64_t* hist)
 {
-    const char* fn = "accel_scores_confidence_interp";
-    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
-    if (!scores) return fail(ACCEL_ERR_ARG, "%s: scores is NULL", fn);
-    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist, true, labels,
-                                 labels_pitch))
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevTemps t;
-    const ConfStage cs(n, h, w, conf, margin, second, hist, labels);
-    const float* s = static_cast<const float*>(t.upload(scores, (size_t)n * ncls * H * W * sizeof(float)));
-    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
-    if (!s || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
-    return confidence_to_host(fn, s, base, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second, second_pitch,
-                              hist, ctx->stream, true, labels, labels_pitch);
+    return ctx_confidence("accel_scores_confidence_interp", ctx, scores, true, n, ncls, H, W, out_h, out_w, h, w, is_prob,
+                          {labels, labels_pitch, conf, conf_pitch, margin, margin_pitch, second, second_pitch, reinterpret_cast<unsigned long long*>(hist)});
 }
 
 extern "C" int accel_model_confidence_interp(accel_model* m, int n, int out_h, int out_w, int h, int w, int is_prob, uint8_t* labels, size_t labels_pitch,
                                              uint8_t* conf, size_t conf_pitch, float* margin, size_t margin_pitch, uint8_t* second, size_t second_pitch,
                                              uint64_t* hist, int dst_on_device)
 {
-    const char* fn = "accel_model_confidence_interp";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const float* scores = nullptr;
-    int ncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
-    if (int rc = confidence_args(fn, n, ncls, H, W, out_h, out_w, h, w, conf, conf_pitch, margin, margin_pitch, second, second_pitch, hist, true, labels,
-                                 labels_pitch))
-        return rc;
-    hipStream_t st = m->ctx->stream;
-    if (dst_on_device) {
-        if (reinterpret_cast<uintptr_t>(margin) % 4) return fail(ACCEL_ERR_ARG, "%s: margin = %p, device floats must be 4-byte aligned", fn, (void*)margin);
-        if (reinterpret_cast<uintptr_t>(hist) % 8) return fail(ACCEL_ERR_ARG, "%s: hist = %p, device words must be 8-byte aligned", fn, (void*)hist);
-        HIP_TRY(hipSetDevice(m->ctx->device));
-        HIP_TRY(launch_scores_confidence(scores, n, ncls, H, W, out_h, out_w, h, w, is_prob, labels, labels_pitch, conf, conf_pitch, margin, margin_pitch,
-                                         second, second_pitch, reinterpret_cast<unsigned long long*>(hist), st));
-        return 0;
-    }
-    const ConfStage cs(n, h, w, conf, margin, second, hist, labels);
-    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
-    return confidence_to_host(fn, scores, m->stage_out.ptr, cs, n, ncls, H, W, out_h, out_w, h, w, is_prob, conf, conf_pitch, margin, margin_pitch, second,
-                              second_pitch, hist, st, true, labels, labels_pitch);
+    return model_confidence("accel_model_confidence_interp", m, true, n, out_h, out_w, h, w, is_prob,
+                            {labels, labels_pitch, conf, conf_pitch, margin, margin_pitch, second, second_pitch, reinterpret_cast<unsigned long long*>(hist)},
+                            dst_on_device);
 }
 
 // ---- labels from interpolated scores (scores_labels.hip) ------------------------------------------------------------------------------------
-// What the four entry points share, checked before anything is enqueued: every message names the argument at fault.
-static int scores_labels_args(const char* fn, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w)
-{
-    if (ncls != 2 && ncls != 19 && ncls != 21) return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the scores must have 2, 19 or 21 classes", fn, ncls);
-    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
-    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
-    return 0;
-}
-
 extern "C" int accel_scores_labels(accel_ctx* ctx, const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w,
                                    uint8_t* dst, size_t dst_pitch)
 {
@@ -1010,73 +1081,6 @@ extern "C" int accel_scores_labels(accel_ctx* ctx, const float* scores, int n, i
     HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
-}
-
-extern "C" int accel_model_scores_labels(accel_model* m, int n, int out_h, int out_w, int h, int w, uint8_t* dst, size_t dst_pitch, int dst_on_device)
-{
-    const char* fn = "accel_model_scores_labels";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
-    const float* scores = nullptr;
-    int ncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
-    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
-    if (dst_on_device) HIP_TRY(hipSetDevice(m->ctx->device));
-    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
-        return launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, d, pitch, st);
-    });
-}
-
-extern "C" int accel_model_scores_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
-                                           int gt_on_device)
-{
-    const char* fn = "accel_model_scores_hist_add";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
-    const float* scores = nullptr;
-    int sncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &sncls, &H, &W)) return rc;
-    if (int rc = scores_labels_args(fn, n, sncls, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
-    if (int rc = ncls_arg(fn, ncls)) return rc;
-    unsigned long long* hist = nullptr;
-    if (int rc = model_hist(fn, m, ncls, &hist)) return rc;
-    hipStream_t st = m->ctx->stream;
-    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
-    unsigned char* lab = m->interp_labels.ptr;
-    const unsigned char* g = gt;
-    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
-    HIP_TRY(launch_scores_labels(scores, n, sncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
-    HIP_TRY(launch_labels_hist(lab, n, h, w, h, w, g, h, w, gt_pitch, ncls, hist, st));       // the scratch at the identity geometry
-    m->hist_ncls = ncls;
-    return 0;
-}
-
-extern "C" int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h, int w, const uint8_t* palette_rgb, int rgb_order,
-                                         const uint8_t* frame_bgr, size_t frame_pitch, int alpha, int frame_on_device,
-                                         uint8_t* dst, size_t dst_pitch, int dst_on_device)
-{
-    const char* fn = "accel_model_scores_colour";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    if (!palette_rgb) return fail(ACCEL_ERR_ARG, "%s: palette_rgb is NULL", fn);
-    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
-    const float* scores = nullptr;
-    int ncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
-    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 3)) return rc;
-    if (frame_bgr) if (int rc = pitch_arg(fn, "frame_pitch", frame_pitch, w, 3)) return rc;
-    if (int rc = alpha_arg(fn, alpha)) return rc;
-    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
-    unsigned char* lab = m->interp_labels.ptr;
-    const unsigned char* f = frame_bgr;
-    if (frame_bgr && !frame_on_device) if (int rc = stage_in(m, frame_bgr, (size_t)n * h * frame_pitch, &f)) return rc;
-    return result_rows(m, dst, dst_pitch, dst_on_device, (size_t)3 * w, (size_t)n * h, [&](unsigned char* d, size_t pitch, hipStream_t st) {
-        const hipError_t e = launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st);
-        if (e != hipSuccess) return e;
-        return launch_labels_colour(lab, n, h, w, h, w, h, w, palette_rgb, rgb_order, f, frame_pitch, alpha, d, pitch, st);   // the scratch at the identity geometry
-    });
 }
 
 // ---- the overlay in the frame's own format (overlay_yuv.hip) ---------------------------------------------------------------------------------
@@ -1161,44 +1165,36 @@ static int overlay_frames(accel_model* m, int n, const accel_yuv_layout& lay, co
     return 0;
 }
 
+static int model_overlay_yuv(const char* fn, accel_model* m, LabelSource::Kind kind, int n, int out_h, int out_w, const accel_yuv_layout* layout,
+                             const uint16_t* palette_ycc, int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    accel_yuv_layout lay;
+    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, frame_on_device ? frame : nullptr, dst, dst_on_device ? dst : nullptr, &lay)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, lay.h, lay.w)) return rc;
+    if (int rc = src.reserve()) return rc;
+    return overlay_frames(m, n, lay, palette_ycc, alpha, frame, frame_on_device, dst, dst_on_device,
+                          [&](const unsigned char* f, unsigned char* d, const YuvLayout& y, hipStream_t st) -> int {
+        HIP_TRY(src.enqueue(st));
+        HIP_TRY(launch_overlay_yuv(src.maps, n, src.H, src.W, src.out_h, src.out_w, y, palette_ycc, alpha, f, d, st));
+        return 0;
+    });
+}
+
 extern "C" int accel_model_labels_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
                                               int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device)
 {
-    const char* fn = "accel_model_labels_overlay_yuv";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const unsigned char* labels = nullptr;
-    if (int rc = model_labels(fn, m, n, &labels)) return rc;
-    const int H = m->labels_h, W = m->labels_w;
-    accel_yuv_layout lay;
-    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, frame_on_device ? frame : nullptr, dst, dst_on_device ? dst : nullptr, &lay)) return rc;
-    if (int rc = results_args(fn, n, H, W, out_h, out_w, lay.h, lay.w)) return rc;
-    return overlay_frames(m, n, lay, palette_ycc, alpha, frame, frame_on_device, dst, dst_on_device,
-                          [&](const unsigned char* f, unsigned char* d, const YuvLayout& y, hipStream_t st) -> int {
-        HIP_TRY(launch_overlay_yuv(labels, n, H, W, out_h, out_w, y, palette_ycc, alpha, f, d, st));
-        return 0;
-    });
+    return model_overlay_yuv("accel_model_labels_overlay_yuv", m, LabelSource::NEAREST, n, out_h, out_w, layout, palette_ycc, alpha, frame,
+                             frame_on_device, dst, dst_on_device);
 }
 
 extern "C" int accel_model_scores_overlay_yuv(accel_model* m, int n, int out_h, int out_w, const accel_yuv_layout* layout, const uint16_t* palette_ycc,
                                               int alpha, const uint8_t* frame, int frame_on_device, uint8_t* dst, int dst_on_device)
 {
-    const char* fn = "accel_model_scores_overlay_yuv";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const float* scores = nullptr;
-    int ncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &ncls, &H, &W)) return rc;
-    accel_yuv_layout lay;
-    if (int rc = overlay_args(fn, n, layout, palette_ycc, alpha, frame, frame_on_device ? frame : nullptr, dst, dst_on_device ? dst : nullptr, &lay)) return rc;
-    const int h = lay.h, w = lay.w;
-    if (int rc = scores_labels_args(fn, n, ncls, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
-    unsigned char* lab = m->interp_labels.ptr;
-    return overlay_frames(m, n, lay, palette_ycc, alpha, frame, frame_on_device, dst, dst_on_device,
-                          [&](const unsigned char* f, unsigned char* d, const YuvLayout& y, hipStream_t st) -> int {
-        HIP_TRY(launch_scores_labels(scores, n, ncls, H, W, out_h, out_w, h, w, lab, (size_t)w, st));
-        HIP_TRY(launch_overlay_yuv(lab, n, h, w, h, w, y, palette_ycc, alpha, f, d, st));       // the scratch at the identity geometry
-        return 0;
-    });
+    return model_overlay_yuv("accel_model_scores_overlay_yuv", m, LabelSource::INTERPOLATED, n, out_h, out_w, layout, palette_ycc, alpha, frame,
+                             frame_on_device, dst, dst_on_device);
 }
 
 // ---- frame change: the measure behind content-adaptive key frames (frame_change.hip) ------------------------------------------------------------
@@ -1224,11 +1220,10 @@ static int frame_change_args(const char* fn, int n, int H, int W, int out_h, int
 }
 
 // the device side of a comparison whose results go to the host: changed (n words), sad (n words), mask (tight rows of gw bytes), each part 256-byte aligned
-struct ChangeStage {
-    size_t changed = 0, sad = 0, mask = 0, bytes = 0;
+struct ChangeStage : Carved {
+    size_t changed = 0, sad = 0, mask = 0;
     ChangeStage(int n, int gh, int gw, bool c, bool s, bool m)
     {
-        auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) / 256 * 256; return at; };
         if (c) changed = take((size_t)n * sizeof(uint32_t));
         if (s) sad = take((size_t)n * sizeof(uint64_t));
         if (m) mask = take((size_t)n * gh * gw);
@@ -1344,12 +1339,11 @@ static int summary_args(const char* fn, int n, int H, int W, int out_h, int out_
 }
 
 // the device side of a summary whose results go to the host: stats (n x ncls x 3 words), box (n x ncls x 4), trans (n x ncls x ncls), each part 256-byte aligned
-struct SummaryStage {
-    size_t stats = 0, box = 0, trans = 0, bytes = 0, sb, bb, tb;
+struct SummaryStage : Carved {
+    size_t stats = 0, box = 0, trans = 0, sb, bb, tb;
     SummaryStage(int n, int ncls, bool s, bool b, bool t)
         : sb((size_t)n * ncls * 3 * sizeof(uint64_t)), bb((size_t)n * ncls * 4 * sizeof(int32_t)), tb((size_t)n * ncls * ncls * sizeof(uint64_t))
     {
-        auto take = [&](size_t b_) { const size_t at = bytes; bytes += (b_ + 255) / 256 * 256; return at; };
         if (s) stats = take(sb);
         if (b) box = take(bb);
         if (t) trans = take(tb);
@@ -1398,26 +1392,28 @@ extern "C" int accel_labels_summary(accel_ctx* ctx, const uint8_t* labels, int n
     return 0;
 }
 
-// what the two model-level forms are told besides the geometry
-static int model_summary_args(const char* fn, int track, const void* stats, const void* box, const void* trans, int dst_on_device, const int* compared)
+// what the two model-level forms share: the summary of the n maps of `src` at the source size, tracked against the model's kept map if asked
+static int model_summary(const char* fn, accel_model* m, LabelSource::Kind kind, int n, int out_h, int out_w, int h, int w, int ncls, int track,
+                         uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared)
 {
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    if (int rc = ncls_arg(fn, ncls)) return rc;
     if (!compared) return fail(ACCEL_ERR_ARG, "%s: compared is NULL", fn);
     if (!stats && !box && !trans) return fail(ACCEL_ERR_ARG, "%s: stats, box and trans are all NULL: nothing to compute", fn);
     if (trans && !track) return fail(ACCEL_ERR_ARG, "%s: trans is asked for with track = 0: transitions need the kept map", fn);
     if (dst_on_device) {
-        if (reinterpret_cast<uintptr_t>(stats) % 8) return fail(ACCEL_ERR_ARG, "%s: stats = %p, device words must be 8-byte aligned", fn, stats);
-        if (reinterpret_cast<uintptr_t>(trans) % 8) return fail(ACCEL_ERR_ARG, "%s: trans = %p, device words must be 8-byte aligned", fn, trans);
-        if (reinterpret_cast<uintptr_t>(box) % 4) return fail(ACCEL_ERR_ARG, "%s: box = %p, device words must be 4-byte aligned", fn, box);
+        if (reinterpret_cast<uintptr_t>(stats) % 8) return fail(ACCEL_ERR_ARG, "%s: stats = %p, device words must be 8-byte aligned", fn, (void*)stats);
+        if (reinterpret_cast<uintptr_t>(trans) % 8) return fail(ACCEL_ERR_ARG, "%s: trans = %p, device words must be 8-byte aligned", fn, (void*)trans);
+        if (reinterpret_cast<uintptr_t>(box) % 4) return fail(ACCEL_ERR_ARG, "%s: box = %p, device words must be 4-byte aligned", fn, (void*)box);
     }
-    return 0;
-}
-
-// the summary of n maps in device memory (checked arguments), tracked against the model's kept map if asked
-static int model_summary(accel_model* m, const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, int track,
-                         uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared)
-{
     hipStream_t st = m->ctx->stream;
     HIP_TRY(hipSetDevice(m->ctx->device));
+    if (int rc = src.reserve()) return rc;
+    HIP_TRY(src.enqueue(st));
     accel_model::KeptLabels& k = m->kept_labels;
     bool cmp = false;
     unsigned char* kept = nullptr;
@@ -1430,12 +1426,14 @@ static int model_summary(accel_model* m, const unsigned char* labels, int n, int
     if (!cmp) trans = nullptr;
     const unsigned char* prev = trans ? kept : nullptr;
     if (dst_on_device) {
-        HIP_TRY(launch_labels_summary(labels, n, H, W, out_h, out_w, h, w, ncls, prev, (size_t)w, reinterpret_cast<unsigned long long*>(stats), box,
-                                      reinterpret_cast<unsigned long long*>(trans), kept, (size_t)w, st));
+        HIP_TRY(launch_labels_summary(src.maps, n, src.H, src.W, src.out_h, src.out_w, h, w, ncls, prev, (size_t)w,
+                                      reinterpret_cast<unsigned long long*>(stats), box, reinterpret_cast<unsigned long long*>(trans), kept, (size_t)w, st));
     } else {
         const SummaryStage ss(n, ncls, stats, box, trans);
         if (int rc = m->stage_out.reserve(m->ctx->device, ss.bytes)) return rc;
-        if (int rc = summary_to_host(labels, n, H, W, out_h, out_w, h, w, ncls, prev, (size_t)w, m->stage_out.ptr, ss, stats, box, trans, kept, (size_t)w, st)) return rc;
+        if (int rc = summary_to_host(src.maps, n, src.H, src.W, src.out_h, src.out_w, h, w, ncls, prev, (size_t)w, m->stage_out.ptr, ss, stats, box, trans,
+                                     kept, (size_t)w, st))
+            return rc;
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (track) { k.n = n; k.h = h; k.w = w; k.ncls = ncls; }
@@ -1446,31 +1444,14 @@ static int model_summary(accel_model* m, const unsigned char* labels, int n, int
 extern "C" int accel_model_labels_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track, uint64_t* stats, int32_t* box,
                                           uint64_t* trans, int dst_on_device, int* compared)
 {
-    const char* fn = "accel_model_labels_summary";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const unsigned char* labels = nullptr;
-    if (int rc = model_labels(fn, m, n, &labels)) return rc;
-    const int H = m->labels_h, W = m->labels_w;
-    if (int rc = summary_args(fn, n, H, W, out_h, out_w, h, w, ncls)) return rc;
-    if (int rc = model_summary_args(fn, track, stats, box, trans, dst_on_device, compared)) return rc;
-    return model_summary(m, labels, n, H, W, out_h, out_w, h, w, ncls, track, stats, box, trans, dst_on_device, compared);
+    return model_summary("accel_model_labels_summary", m, LabelSource::NEAREST, n, out_h, out_w, h, w, ncls, track, stats, box, trans, dst_on_device, compared);
 }
 
 extern "C" int accel_model_scores_summary(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int track, uint64_t* stats, int32_t* box,
                                           uint64_t* trans, int dst_on_device, int* compared)
 {
-    const char* fn = "accel_model_scores_summary";
-    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
-    const float* scores = nullptr;
-    int sncls = 0, H = 0, W = 0;
-    if (int rc = model_scores(fn, m, n, &scores, &sncls, &H, &W)) return rc;
-    if (int rc = scores_labels_args(fn, n, sncls, H, W, out_h, out_w, h, w)) return rc;
-    if (int rc = ncls_arg(fn, ncls)) return rc;
-    if (int rc = model_summary_args(fn, track, stats, box, trans, dst_on_device, compared)) return rc;
-    if (int rc = m->interp_labels.reserve(m->ctx->device, (size_t)n * h * w)) return rc;
-    unsigned char* lab = m->interp_labels.ptr;
-    HIP_TRY(launch_scores_labels(scores, n, sncls, H, W, out_h, out_w, h, w, lab, (size_t)w, m->ctx->stream));
-    return model_summary(m, lab, n, h, w, h, w, h, w, ncls, track, stats, box, trans, dst_on_device, compared);      // the scratch at the identity geometry
+    return model_summary("accel_model_scores_summary", m, LabelSource::INTERPOLATED, n, out_h, out_w, h, w, ncls, track, stats, box, trans, dst_on_device,
+                         compared);
 }
 
 extern "C" int accel_model_labels_forget(accel_model* m)

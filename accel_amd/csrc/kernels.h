@@ -183,23 +183,26 @@ hipError_t launch_overlay_yuv(const unsigned char* labels, int n, int H, int W, 
                               int alpha, const unsigned char* frame, unsigned char* dst, hipStream_t st);
 // confidence of finished frames (confidence.hip): n x ncls x H x W fp32 scores (NCHW, the layout of `logits`; ncls in {2, 19, 21}) in the geometry
 // above -> per source pixel conf = min(255, floor(256 * largest softmax probability)) (float64; is_prob: the scores are probabilities, no
-// exponential), margin = l_top1 - l_top2 (fp32), second = the runner-up class, and hist = n x 256 counts of the conf levels per frame (overwritten).
-// A null output is left out; pitches in bytes (margin_pitch a multiple of 4).  All pointers are device memory; the kernel only reads `scores`
-hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob, unsigned char* conf,
-                             size_t conf_pitch, float* margin, size_t margin_pitch, unsigned char* second, size_t second_pitch, unsigned long long* hist,
-                             hipStream_t st);
+// exponential), margin = v_top1 - v_top2, second = the runner-up class, and hist = n x 256 counts of the conf levels per frame (overwritten).
+// interp = false: of the stored scores of the nearest map pixel (margin: one fp32 subtraction; utils/image.py confidence_host), no labels.
+// interp = true: of the ncls values interpolated as launch_scores_labels interpolates them (float64 throughout; margin = float(v_top1 - v_top2);
+// utils/image.py confidence_interpolated_host), and labels = their argmax, what launch_scores_labels writes.
+// A null output is left out, at least one is given; pitches in bytes (margin_pitch a multiple of 4).  All pointers are device memory; the kernel
+// only reads `scores`
+struct ConfOut {
+    unsigned char* labels; size_t labels_pitch;         // the interpolated form only
+    unsigned char* conf; size_t conf_pitch;
+    float* margin; size_t margin_pitch;                 // bytes, a multiple of 4
+    unsigned char* second; size_t second_pitch;
+    unsigned long long* hist;                           // n x 256
+};
+hipError_t launch_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob, bool interp,
+                             const ConfOut& o, hipStream_t st);
 // labels from interpolated scores (scores_labels.hip): the same scores and geometry vocabulary -> per source pixel the first-max argmax of the
 // ncls planes interpolated bilinearly (half-pixel centres, taps clamped to the valid region, float64 blend: utils/image.py
 // labels_interpolated_host), n x h x w uint8 with rows dst_pitch bytes apart.  Device pointers; the kernel only reads `scores`
 hipError_t launch_scores_labels(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch,
                                 hipStream_t st);
-// confidence of interpolated scores, with their labels (scores_confidence.hip): the same scores and geometry -> per source pixel, from the ncls values
-// v_k interpolated as launch_scores_labels interpolates them, labels = its argmax, conf / margin / second / hist as launch_confidence but of the v_k
-// (float64 throughout; margin = float(v_top1 - v_top2); utils/image.py confidence_interpolated_host).  A null output is left out, at least one is
-// given; pitches in bytes (margin_pitch a multiple of 4); hist is overwritten.  Device pointers; the kernel only reads `scores`
-hipError_t launch_scores_confidence(const float* scores, int n, int ncls, int H, int W, int out_h, int out_w, int h, int w, int is_prob,
-                                    unsigned char* labels, size_t labels_pitch, unsigned char* conf, size_t conf_pitch, float* margin, size_t margin_pitch,
-                                    unsigned char* second, size_t second_pitch, unsigned long long* hist, hipStream_t st);
 // frame change (frame_change.hip): the image input img (n x 3 x H x W fp32, planes R, G, B, valid region out_h x out_w) -> its signature, n x gh x gw
 // int32 sums of 2 qR + 5 qG + qB over cells of cell x cell pixels (gh = ceil(out_h / cell), gw alike; q = rint(clamp(x, +-512) * 8)), and, against
 // the signature sig_key of a key frame (null: signature only), per frame changed = the cells with |S - S_key| > level_q * area, sad = the sum of the

@@ -23,33 +23,14 @@
 // VEC: the rows of prev and kept (and, at the identity geometry, of labels) allow 16-byte accesses (pitches % 16 == 0, aligned bases); units that cross
 // the end of a row, and everything else, go byte by byte.  Nothing outside out_h x out_w of `labels` is read.
 #include "kernels.h"
+#include "labels_nearest.h"
 #include <stdint.h>
 
 namespace {
 
-// the label-map column of source column x and the exact stepping to the columns after it (results_u8.hip)
-struct Column {
-    int sx, rem, qw, rw, w, last;
-    __device__ __forceinline__ Column(int x, int out_w, int w_) : w(w_), last(out_w - 1)
-    {
-        const unsigned p = (unsigned)x * (unsigned)out_w;      // < 2^31: both are image sizes (checked by the caller)
-        sx = (int)(p / (unsigned)w_);
-        rem = (int)(p - (unsigned)sx * (unsigned)w_);
-        qw = out_w / w_;
-        rw = out_w - qw * w_;
-    }
-    __device__ __forceinline__ int col() const { return min(sx, last); }
-    __device__ __forceinline__ void next()
-    {
-        sx += qw; rem += rw;
-        if (rem >= w) { rem -= w; ++sx; }
-    }
-};
-
-__device__ __forceinline__ int source_row(int y, int out_h, int h)
-{
-    return min((int)((unsigned)y * (unsigned)out_h / (unsigned)h), out_h - 1);
-}
+using nearest::Column;
+using nearest::source_row;
+using nearest::aligned;
 
 struct SummaryMaps {
     const unsigned char* prev; size_t prev_pitch;       // n x h rows, or null: nothing to compare with
@@ -211,8 +192,6 @@ __global__ __launch_bounds__(256) void labels_summary_init_kernel(unsigned long 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_trans; i += stride) trans[i] = 0ull;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_box; i += stride) box[i] = (i & 3) == 0 ? w : (i & 3) == 1 ? h : -1;
 }
-
-inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-// The histogram of conf levels per frame, as confidence.hip and scores_confidence.hip both count it: runs of equal levels in a register, then 256
+// The histogram of conf levels per frame, as both forms of confidence.hip count it: runs of equal levels in a register, then 256
 // block-private 32-bit LDS bins, then one 64-bit atomic per non-zero bin per block into the frame's 256 words.  A block of 256 threads that never
 // spans two frames; the bins are zeroed (and a barrier passed) before the first count.  Integer sums: exact, independent of the order of arrival.
 #pragma once

@@ -16,6 +16,7 @@
 // Bytes that are not samples (between rows, between planes, after a frame) are neither read nor written.
 // A bandwidth kernel: about 1 label byte + the frame's bytes in, the frame's bytes out.
 #include "frames_yuv.h"
+#include "labels_nearest.h"
 
 namespace {
 
@@ -23,29 +24,8 @@ using namespace yuv;      // the formats, Layout, Patch, word10
 
 struct TableYcc { uint16_t ycc[768]; };       // passed BY VALUE: 1536 bytes of kernel argument, no allocation, ordered with the stream for free
 
-// the label-map column of source column x and the exact stepping to the columns after it, and the row: the arithmetic of results_u8.hip
-struct Column {
-    int sx, rem, qw, rw, w, last;
-    __device__ __forceinline__ Column(int x, int out_w, int w_) : w(w_), last(out_w - 1)
-    {
-        const unsigned p = (unsigned)x * (unsigned)out_w;      // < 2^31: both are image sizes (checked by the caller, results_args)
-        sx = (int)(p / (unsigned)w_);
-        rem = (int)(p - (unsigned)sx * (unsigned)w_);
-        qw = out_w / w_;
-        rw = out_w - qw * w_;
-    }
-    __device__ __forceinline__ int col() const { return min(sx, last); }
-    __device__ __forceinline__ void next()
-    {
-        sx += qw; rem += rw;
-        if (rem >= w) { rem -= w; ++sx; }
-    }
-};
-
-__device__ __forceinline__ int source_row(int y, int out_h, int h)
-{
-    return min((int)((unsigned)y * (unsigned)out_h / (unsigned)h), out_h - 1);
-}
+using nearest::Column;
+using nearest::source_row;
 
 __device__ __forceinline__ void store10(unsigned char* p, unsigned v) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)(v << 6); }
 

@@ -10,33 +10,14 @@
 // out_w / w with the remainder carried (Bresenham).  Everything is integer arithmetic on bytes: every result has one correct value.
 // Bandwidth kernels: bytes in + bytes out.  They only READ `labels`.
 #include "kernels.h"
+#include "labels_nearest.h"
 #include <stdint.h>
 
 namespace {
 
-// the label-map column of source column x and the exact stepping to the columns after it
-struct Column {
-    int sx, rem, qw, rw, w, last;
-    __device__ __forceinline__ Column(int x, int out_w, int w_) : w(w_), last(out_w - 1)
-    {
-        const unsigned p = (unsigned)x * (unsigned)out_w;      // < 2^31: both are image sizes (checked by the caller, results_args)
-        sx = (int)(p / (unsigned)w_);
-        rem = (int)(p - (unsigned)sx * (unsigned)w_);
-        qw = out_w / w_;
-        rw = out_w - qw * w_;
-    }
-    __device__ __forceinline__ int col() const { return min(sx, last); }
-    __device__ __forceinline__ void next()
-    {
-        sx += qw; rem += rw;
-        if (rem >= w) { rem -= w; ++sx; }
-    }
-};
-
-__device__ __forceinline__ int source_row(int y, int out_h, int h)
-{
-    return min((int)((unsigned)y * (unsigned)out_h / (unsigned)h), out_h - 1);
-}
+using nearest::Column;
+using nearest::source_row;
+using nearest::aligned;
 
 // ---- labels at the source size -------------------------------------------------------------------------------------------------------
 // A thread takes V consecutive pixels of one destination row.  IDENT with V = 16 / 4: one uint4 / dword load and store (the launcher has
@@ -223,8 +204,6 @@ __global__ __launch_bounds__(256) void labels_colour_kernel(const unsigned char*
             if (x0 + k / 3 < w) out[k] = o[k];
     }
 }
-
-inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
 

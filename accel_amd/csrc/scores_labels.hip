@@ -5,9 +5,8 @@
 // The geometry vocabulary is that of results_u8.hip and confidence.hip: one valid region out_h x out_w in the top-left corner of the H x W
 // map, one source size h x w.  The arithmetic restates accel_amd/utils/image.py labels_interpolated_host bit for bit.
 //
-// Taps: scores_interp.h (integer arithmetic, clamped to the valid region -- the padding is never read -- one IEEE division per weight).
-// Blend, in float64, each operation rounded on its own (no fma), in the order of frames::blend; a<row><col> the fp32 taps as doubles:
-//     gx = 1 - fx;  gy = 1 - fy;  top = a00 * gx + a01 * fx;  bot = a10 * gx + a11 * fx;  v_k = top * gy + bot * fy
+// Taps, their loads and the blend: scores_interp.h (integer taps clamped to the valid region -- the padding is never read -- one IEEE division
+// per weight, a float64 blend with each operation rounded on its own), shared with the interpolated form of confidence.hip.
 // Label: the first k with the largest v_k (ascending scan, strict >): the tie rule of `labels`.
 // At h x w == out_h x out_w, fx = fy = 0 and v_k is the stored score: the result is the crop of `labels`.
 // Scores are assumed FINITE: a pixel with a non-finite tap is unspecified (inf * 0 arises in the blend).
@@ -18,13 +17,13 @@
 // an fp32 compare chain (the blend is the identity there) and one dword store of four labels.
 // Grid-stride loop, no LDS, no atomics.  blockIdx.z is the frame.  The kernel only READS the scores.
 #include "kernels.h"
+#include "labels_nearest.h"
 #include "scores_interp.h"
 #include <stdint.h>
 
 namespace {
 
-using interp::Tap;
-using interp::tap;
+using nearest::aligned;
 
 template <int NCLS, int V>
 __global__ __launch_bounds__(256) void scores_labels_kernel(const float* __restrict__ scores, int H, int W, int out_h, int out_w, int h, int w,
@@ -58,35 +57,24 @@ __global__ __launch_bounds__(256) void scores_labels_kernel(const float* __restr
             }
             *reinterpret_cast<uint32_t*>(out) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
         } else {
-#pragma clang fp contract(off)
-            const Tap ty = tap(y, h, out_h), tx = tap(x0, w, out_w);
+            const interp::Tap ty = interp::tap(y, h, out_h), tx = interp::tap(x0, w, out_w);
             const float* r0 = img + (size_t)ty.i0 * W;
             const float* r1 = img + (size_t)ty.i1 * W;
-            float a00[NCLS], a01[NCLS], a10[NCLS], a11[NCLS];
+            interp::Taps a[NCLS];
 #pragma unroll
-            for (int k = 0; k < NCLS; ++k) {
-                a00[k] = r0[(size_t)k * plane + tx.i0]; a01[k] = r0[(size_t)k * plane + tx.i1];
-                a10[k] = r1[(size_t)k * plane + tx.i0]; a11[k] = r1[(size_t)k * plane + tx.i1];
-            }
-            const double fx = tx.f, fy = ty.f, gx = 1.0 - fx, gy = 1.0 - fy;
+            for (int k = 0; k < NCLS; ++k) a[k] = interp::load_taps(r0, r1, (size_t)k * plane, tx.i0, tx.i1);
+            const interp::Weights wt(ty, tx);
             unsigned best = 0;
             double bv = 0.0;
 #pragma unroll
             for (int k = 0; k < NCLS; ++k) {
-                const double t0 = (double)a00[k] * gx, t1 = (double)a01[k] * fx;
-                const double top = t0 + t1;
-                const double b0 = (double)a10[k] * gx, b1 = (double)a11[k] * fx;
-                const double bot = b0 + b1;
-                const double u0 = top * gy, u1 = bot * fy;
-                const double v = u0 + u1;
+                const double v = interp::blend(a[k], wt);
                 if (k == 0 || v > bv) { bv = v; best = (unsigned)k; }
             }
             out[0] = (unsigned char)best;
         }
     }
 }
-
-inline bool aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 template <int NCLS>
 hipError_t launch_ncls(const float* scores, int n, int H, int W, int out_h, int out_w, int h, int w, unsigned char* dst, size_t dst_pitch, hipStream_t st)

@@ -1018,18 +1018,21 @@ class Model(object):
         check(lib().accel_model_hist_read(self.handle, _fp(out), int(ncls), int(bool(clear))))
         return out
 
+    def _colour(self, fn, n, out_h, out_w, h, w, palette, frames, alpha, rgb, width, out):
+        f, fp = None, 0
+        if frames is not None:
+            f, fn_, fh, fw, fp = _u8_frames(frames, width)
+            if (fn_, fh, fw) != (int(n), int(h), int(w)):
+                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn_, fh, fw, n, h, w))
+        out, pitch = _result_rows(out, int(n), int(h), int(w), 3)
+        check(fn(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
+                 None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
+        return out
+
     def labels_colour(self, n, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
         """accel_model_labels_colour: the first n maps of `labels` as n x h x w x 3 colours at the source size, blended with host
         `frames` (uint8 BGR, see _u8_frames) when given"""
-        f, fp = None, 0
-        if frames is not None:
-            f, fn, fh, fw, fp = _u8_frames(frames, width)
-            if (fn, fh, fw) != (int(n), int(h), int(w)):
-                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn, fh, fw, n, h, w))
-        out, pitch = _result_rows(out, int(n), int(h), int(w), 3)
-        check(lib().accel_model_labels_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
-                                              None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
-        return out
+        return self._colour(lib().accel_model_labels_colour, n, out_h, out_w, h, w, palette, frames, alpha, rgb, width, out)
 
     def labels_colour_device(self, dst_ptr, n, out_h, out_w, h, w, pitch, palette, frame_ptr=None, frame_pitch=0, alpha=256, rgb=True):
         """the same into caller-owned HBM, blended with frames that are in HBM already (enqueued, no host wait)"""
@@ -1162,15 +1165,7 @@ class Model(object):
 
     def scores_colour(self, n, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
         """accel_model_scores_colour: labels_colour with the labels of the interpolated scores"""
-        f, fp = None, 0
-        if frames is not None:
-            f, fn, fh, fw, fp = _u8_frames(frames, width)
-            if (fn, fh, fw) != (int(n), int(h), int(w)):
-                raise ValueError("frames of %d x %d x %d for a result of %d x %d x %d" % (fn, fh, fw, n, h, w))
-        out, pitch = _result_rows(out, int(n), int(h), int(w), 3)
-        check(lib().accel_model_scores_colour(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), _fp(_palette(palette)), int(bool(rgb)),
-                                              None if f is None else _fp(f), fp, int(alpha), 0, _fp(out), pitch, 0))
-        return out
+        return self._colour(lib().accel_model_scores_colour, n, out_h, out_w, h, w, palette, frames, alpha, rgb, width, out)
 
     # ---- the overlay in the frame's own format: they only READ `labels` / `logits` -------------------------------------------------
     def _overlay_yuv(self, fn, n, out_h, out_w, buf, fmt, h, w, table, alpha, layout):

@@ -440,7 +440,7 @@ int accel_model_scores_colour(accel_model* m, int n, int out_h, int out_w, int h
 /* ---- finished frames: confidence of interpolated scores, with their labels ---------------------------------------------
  * The confidence block above describes the NEAREST map pixel; the labels of the block above are the argmax of INTERPOLATED
  * scores.  For a frame that was resampled on the way in the two do not speak of the same winner.  These two calls finish a
- * source pixel from the interpolated values themselves, in ONE pass over the scores (csrc/scores_confidence.hip), and can
+ * source pixel from the interpolated values themselves, in ONE pass over the scores (the interpolated form of csrc/confidence.hip), and can
  * hand out the label found on the way.  `scores`, ncls and the geometry as above; v_k are the ncls values of the pixel,
  * taps and blend exactly as in the block above (float64).  Any subset of (a NULL pointer leaves one out, at least one):
  *   labels   n x h x w uint8    the first k with the largest v_k: what accel_scores_labels writes

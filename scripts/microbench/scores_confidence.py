@@ -1,4 +1,4 @@
-"""What the confidence of interpolated scores costs in one pass with their labels (accel_model_confidence_interp, csrc/scores_confidence.hip)
+"""What the confidence of interpolated scores costs in one pass with their labels (accel_model_confidence_interp, the interpolated form of csrc/confidence.hip)
 against the two-kernel route it replaces at the same geometry -- accel_model_scores_labels (csrc/scores_labels.hip) for the labels plus
 accel_model_confidence (csrc/confidence.hip, the nearest rule) for conf and hist, each reading the logits once -- on models that own a `logits`
 buffer of --frames frames filled with seeded scores.  No network is run: the kernels' time depends on the shapes, not on whose logits they are.
