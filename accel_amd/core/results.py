@@ -8,6 +8,9 @@ source size and takes the argmax there (csrc/scores_labels.hip behind accel_mode
 hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).  `summary` says what
 is in the frame, where, and whether it just changed: per-class areas, coordinate sums and boxes, and the class transitions against the
 previous frame, which is kept in HBM (csrc/labels_summary.hip behind accel_model_labels_summary / _scores_summary / _labels_forget).
+`TrimapEvaluator` counts the confusion matrix in bands around the ground truth's boundaries, where propagated features are damaged first, and
+`boundary_distance` gives the distance map itself (csrc/labels_band.hip behind accel_model_band_hist_add / _scores_band_hist_add /
+_band_hist_read and accel_boundary_distance).
 
 The reference fetches the label map and does all of this in numpy (demo.py:245-266: `.asnumpy()`, fast_hist, the palette PNG); its
 evaluator resizes a prediction to the ground truth with nearest neighbour (lib/dataset/cityscape.py:227).  Here the prediction is at the
@@ -238,3 +241,98 @@ class Evaluator(object):
 
     def per_class_iu(self):
         return per_class_iu(self.hist())
+
+
+def boundary_distance(maps, cap, ctx=None):
+    """The distance of every pixel of label maps ([n x] h x w uint8: ground truth, or fetched predictions) to the nearest boundary: numpy n x h x w
+    uint8 = min(cap, Chebyshev distance to the nearest pixel with a differing 4-neighbour), cap in 1 .. 16 (utils.image.boundary_distance_host, on
+    the GPU: csrc/labels_band.hip behind accel_boundary_distance).  d == 0 is the outline a viewer draws, d < k the band a trimap of width k counts
+    in.  ctx: the runtime.Context to run on; None opens one on device 0 for the call."""
+    if ctx is not None:
+        return ctx.boundary_distance(maps, cap)
+    own = runtime.Context(0)
+    try:
+        return own.boundary_distance(maps, cap)
+    finally:
+        own.close()
+
+
+class TrimapEvaluator(object):
+    """mIoU restricted to bands around the ground truth's boundaries, against the band width (the trimap of the DeepLab papers), counted on the GPU:
+    `add` enqueues one kernel that takes the prediction to the ground truth's size, measures every pixel's distance to the nearest ground-truth
+    boundary and adds to one confusion matrix per distance bucket in the model (csrc/labels_band.hip behind accel_model_band_hist_add /
+    _scores_band_hist_add / _band_hist_read; utils.image.band_hist_host).  widths: 1 to 4 strictly ascending band widths in pixels, 1 .. 16.  The
+    accumulator is the model's band accumulator, separate from the one `Evaluator` uses: both may run on one model.  The evaluator adopts the model
+    of the first handle it is given and reports what was added since then."""
+
+    def __init__(self, num_classes, widths=(1, 2, 4, 8)):
+        from ..utils.image import band_widths
+        self.num_classes = int(num_classes)
+        if not 1 <= self.num_classes <= 32:
+            raise ValueError("num_classes = %d, must be in 1 .. 32" % self.num_classes)
+        self.widths = band_widths(widths)
+        self._m = None
+        self._base = np.zeros((len(self.widths) + 1, self.num_classes, self.num_classes), np.int64)
+
+    def add(self, handle, gt, like=None, interpolate=False):
+        """count `handle`'s labels against ground truth `gt` ([n x] h x w uint8; ids >= num_classes, such as 255, are ignored as classes and
+        still make boundaries).  interpolate=True: `handle` is the LOGITS handle and the labels are those of
+        labels_at_source(handle, like, interpolate=True)"""
+        m = _model(handle, "logits" if interpolate else "labels")
+        if self._m is None:
+            self._base = m.band_hist_read(self.num_classes, len(self.widths)).astype(np.int64)
+            self._m = m
+        elif m is not self._m:
+            raise runtime.AccelError("this evaluator accumulates in another model: one TrimapEvaluator per model")
+        g = np.asarray(gt)
+        if g.ndim == 2:
+            g = g[None]
+        if g.dtype != np.uint8:
+            g = np.where((g >= 0) & (g < 256), g, 255).astype(np.uint8)      # anything outside a byte is ignored either way
+        n, out_h, out_w, h, w = _geometry(handle, like, hw=g.shape[1:3], scores=bool(interpolate))
+        if g.shape[0] != n:
+            raise ValueError("%d label maps but %d ground-truth maps" % (n, g.shape[0]))
+        if interpolate:
+            m.scores_band_hist_add(g, out_h, out_w, self.num_classes, self.widths)
+        else:
+            m.band_hist_add(g, out_h, out_w, self.num_classes, self.widths)
+
+    def buckets(self, clear=False):
+        """the counts per distance bucket so far: int64 (K + 1) x num_classes x num_classes (waits for the GPU)"""
+        if self._m is None:
+            return np.zeros_like(self._base)
+        out = self._m.band_hist_read(self.num_classes, len(self.widths), clear=clear).astype(np.int64) - self._base
+        if clear:
+            self._base[...] = 0
+        return out
+
+    def hist(self, clear=False):
+        """int64 (K + 1) x num_classes x num_classes, rows ground truth, columns prediction: [k] is the BAND of width widths[k] (cumulative),
+        [K] the whole frame"""
+        return self.cumulative(self.buckets(clear=clear))
+
+    @staticmethod
+    def cumulative(buckets):
+        from ..utils.image import band_cumulative
+        return band_cumulative(buckets)
+
+    @staticmethod
+    def iu_of(hist):
+        """per_class_iu of every matrix of a (K + 1) x ncls x ncls array: (K + 1) x ncls"""
+        return np.stack([per_class_iu(h) for h in np.asarray(hist)])
+
+    @staticmethod
+    def miou_of(hist):
+        """the mean IoU over the classes present in every matrix of a (K + 1) x ncls x ncls array: K + 1 floats, nan where a matrix is empty"""
+        iu = TrimapEvaluator.iu_of(hist)
+        out = np.full(iu.shape[0], np.nan)
+        some = ~np.isnan(iu).all(axis=1)
+        out[some] = np.nanmean(iu[some], axis=1)
+        return out
+
+    def per_class_iu(self):
+        return self.iu_of(self.hist())
+
+    def miou(self):
+        """K + 1 floats: the mIoU inside the band of every width, then of the whole frame; nan where a band holds no counted pixel"""
+        return self.miou_of(self.hist())

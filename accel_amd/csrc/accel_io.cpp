@@ -1461,6 +1461,158 @@ extern "C" int accel_model_labels_forget(accel_model* m)
     return 0;
 }
 
+// ---- trimap evaluation: the distance to the ground truth's boundaries and the confusion matrix per band of it (labels_band.hip) ---------------------
+static int widths_arg(const char* fn, const int* widths, int nwidths)
+{
+    if (!widths) return fail(ACCEL_ERR_ARG, "%s: widths is NULL", fn);
+    if (nwidths < 1 || nwidths > 4) return fail(ACCEL_ERR_ARG, "%s: nwidths = %d, must be in 1 .. 4", fn, nwidths);
+    for (int i = 0; i < nwidths; ++i) {
+        if (widths[i] < 1 || widths[i] > 16) return fail(ACCEL_ERR_ARG, "%s: widths[%d] = %d, a width must be in 1 .. 16", fn, i, widths[i]);
+        if (i && widths[i] <= widths[i - 1])
+            return fail(ACCEL_ERR_ARG, "%s: widths[%d] = %d after %d, widths must be strictly ascending", fn, i, widths[i], widths[i - 1]);
+    }
+    return 0;
+}
+
+static int batch_arg(const char* fn, int n)
+{
+    if (n < 1 || n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    return 0;
+}
+
+extern "C" int accel_boundary_distance(accel_ctx* ctx, const uint8_t* maps, int n, int h, int w, size_t pitch, int cap, uint8_t* dst, size_t dst_pitch)
+{
+    const char* fn = "accel_boundary_distance";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!maps) return fail(ACCEL_ERR_ARG, "%s: maps is NULL", fn);
+    if (!dst) return fail(ACCEL_ERR_ARG, "%s: dst is NULL", fn);
+    if (int rc = batch_arg(fn, n)) return rc;
+    if (h < 1 || h > 32768) return fail(ACCEL_ERR_ARG, "%s: h = %d, must be in 1 .. 32768", fn, h);
+    if (w < 1 || w > 32768) return fail(ACCEL_ERR_ARG, "%s: w = %d, must be in 1 .. 32768", fn, w);
+    if (int rc = pitch_arg(fn, "pitch", pitch, w, 1)) return rc;
+    if (int rc = pitch_arg(fn, "dst_pitch", dst_pitch, w, 1)) return rc;
+    if (cap < 1 || cap > 16) return fail(ACCEL_ERR_ARG, "%s: cap = %d, must be in 1 .. 16", fn, cap);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const unsigned char* g = static_cast<const unsigned char*>(t.upload(maps, (size_t)n * h * pitch));
+    unsigned char* d = static_cast<unsigned char*>(t.get((size_t)n * h * w));
+    if (!g || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_boundary_distance(g, n, h, w, pitch, cap, d, (size_t)w, ctx->stream));
+    HIP_TRY(rows_to_host(dst, dst_pitch, d, (size_t)w, (size_t)n * h, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int accel_labels_band_hist(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, const uint8_t* gt, int h, int w,
+                                      size_t gt_pitch, int ncls, const int* widths, int nwidths, uint64_t* hist)
+{
+    const char* fn = "accel_labels_band_hist";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    if (!hist) return fail(ACCEL_ERR_ARG, "%s: hist is NULL", fn);
+    if (int rc = batch_arg(fn, n)) return rc;
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (int rc = widths_arg(fn, widths, nwidths)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const size_t hb = (size_t)(nwidths + 1) * ncls * ncls * sizeof(uint64_t);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    const unsigned char* g = static_cast<const unsigned char*>(t.upload(gt, (size_t)n * h * gt_pitch));
+    unsigned long long* d = static_cast<unsigned long long*>(t.upload(hist, hb));
+    if (!l || !g || !d) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    HIP_TRY(launch_labels_band_hist(l, n, H, W, out_h, out_w, g, h, w, gt_pitch, ncls, widths, nwidths, d, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hist, d, hb, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// the model's band accumulator for counts of `ncls` classes in the bands of `widths`: refused while it holds counts made under other values, allocated and
+// zeroed on first use.  (nwidths + 1) * ncls * ncls words of the 5 * 32 * 32 are in use
+static const size_t BAND_HIST_BYTES = 5 * 32 * 32 * sizeof(unsigned long long);
+
+static int model_band_hist(const char* fn, accel_model* m, int ncls, const int* widths, int nwidths, unsigned long long** hist)
+{
+    accel_model::BandHist& b = m->band_hist;
+    if (b.ncls) {
+        if (b.ncls != ncls)
+            return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the band accumulator holds counts of %d classes since its last clear", fn, ncls, b.ncls);
+        bool same = b.nwidths == nwidths;
+        for (int i = 0; same && widths && i < nwidths; ++i) same = b.widths[i] == widths[i];
+        if (!same) return fail(ACCEL_ERR_ARG, "%s: the band accumulator holds counts of %d other widths since its last clear", fn, b.nwidths);
+    }
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (!b.words) {
+        HIP_TRY(hipMalloc((void**)&b.words, BAND_HIST_BYTES));
+        HIP_TRY(hipMemsetAsync(b.words, 0, BAND_HIST_BYTES, m->ctx->stream));
+    }
+    *hist = b.words;
+    return 0;
+}
+
+static int model_band_hist_add(const char* fn, accel_model* m, LabelSource::Kind kind, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h,
+                               int out_w, int ncls, const int* widths, int nwidths, int gt_on_device)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!gt) return fail(ACCEL_ERR_ARG, "%s: gt is NULL", fn);
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
+    if (int rc = batch_arg(fn, n)) return rc;
+    if (int rc = pitch_arg(fn, "gt_pitch", gt_pitch, w, 1)) return rc;
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (int rc = widths_arg(fn, widths, nwidths)) return rc;
+    unsigned long long* hist = nullptr;
+    if (int rc = model_band_hist(fn, m, ncls, widths, nwidths, &hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    if (int rc = src.reserve()) return rc;
+    const unsigned char* g = gt;
+    if (!gt_on_device) if (int rc = stage_in(m, gt, (size_t)n * h * gt_pitch, &g)) return rc;
+    HIP_TRY(src.enqueue(st));
+    HIP_TRY(launch_labels_band_hist(src.maps, n, src.H, src.W, src.out_h, src.out_w, g, h, w, gt_pitch, ncls, widths, nwidths, hist, st));
+    accel_model::BandHist& b = m->band_hist;
+    b.ncls = ncls; b.nwidths = nwidths;
+    for (int i = 0; i < nwidths; ++i) b.widths[i] = widths[i];
+    return 0;
+}
+
+extern "C" int accel_model_band_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                         const int* widths, int nwidths, int gt_on_device)
+{
+    return model_band_hist_add("accel_model_band_hist_add", m, LabelSource::NEAREST, gt, n, h, w, gt_pitch, out_h, out_w, ncls, widths, nwidths, gt_on_device);
+}
+
+extern "C" int accel_model_scores_band_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                                const int* widths, int nwidths, int gt_on_device)
+{
+    return model_band_hist_add("accel_model_scores_band_hist_add", m, LabelSource::INTERPOLATED, gt, n, h, w, gt_pitch, out_h, out_w, ncls, widths, nwidths,
+                               gt_on_device);
+}
+
+extern "C" int accel_model_band_hist_read(accel_model* m, uint64_t* out, int ncls, int nwidths, int clear)
+{
+    const char* fn = "accel_model_band_hist_read";
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    if (!out) return fail(ACCEL_ERR_ARG, "%s: out is NULL", fn);
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (nwidths < 1 || nwidths > 4) return fail(ACCEL_ERR_ARG, "%s: nwidths = %d, must be in 1 .. 4", fn, nwidths);
+    const size_t hb = (size_t)(nwidths + 1) * ncls * ncls * sizeof(uint64_t);
+    accel_model::BandHist& b = m->band_hist;
+    if (!b.ncls) { memset(out, 0, hb); return 0; }      // nothing added since the last clear: any class count and number of widths may be asked for
+    unsigned long long* hist = nullptr;
+    if (int rc = model_band_hist(fn, m, ncls, nullptr, nwidths, &hist)) return rc;
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(out, hist, hb, hipMemcpyDeviceToHost, st));
+    if (clear) {
+        HIP_TRY(hipMemsetAsync(hist, 0, BAND_HIST_BYTES, st));
+        b.ncls = 0; b.nwidths = 0;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int accel_model_read_async(accel_model* m, const char* buf, void* pinned_dst, size_t bytes)
 {
     if (!m || !buf || !pinned_dst) return fail(ACCEL_ERR_ARG, "accel_model_read_async: NULL argument");

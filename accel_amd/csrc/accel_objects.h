@@ -104,6 +104,17 @@ struct accel_model {
     DevScratch stage_out;
     unsigned long long* hist = nullptr;
     int hist_ncls = 0;
+    // accel_model_band_hist_add / _scores_band_hist_add / _band_hist_read: the confusion matrix per band around the ground truth's boundaries, an
+    // accumulator of its own -- 5 x 32 x 32 words (allocated on first use), of which (nwidths + 1) x ncls x ncls hold counts made under `widths`
+    // (ncls = 0: empty since the last clear)
+    struct BandHist {
+        unsigned long long* words = nullptr;
+        int ncls = 0, nwidths = 0, widths[4] = {0, 0, 0, 0};
+        BandHist() = default;
+        BandHist(const BandHist&) = delete;
+        ~BandHist() { if (words) hipFree(words); }
+    };
+    BandHist band_hist;
     // accel_model_scores_hist_add / _scores_colour: the labels of the interpolated scores at the source size (n x h x w uint8, tight rows)
     // on their way to the counting / colouring kernel
     DevScratch interp_labels;

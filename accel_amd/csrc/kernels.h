@@ -218,6 +218,14 @@ hipError_t launch_frame_change(const float* img, const int* sig_key, int n, int 
 hipError_t launch_labels_summary(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, const unsigned char* prev,
                                  size_t prev_pitch, unsigned long long* stats, int* box, unsigned long long* trans, unsigned char* kept, size_t kept_pitch,
                                  hipStream_t st);
+// trimap evaluation (labels_band.hip).  launch_boundary_distance: n maps of h x w bytes (rows `pitch` apart) -> d = min(cap, Chebyshev distance to the
+// nearest pixel with a differing 4-neighbour inside its frame), 1 <= cap <= 16, as bytes (rows `dst_pitch` apart): utils/image.py boundary_distance_host.
+// launch_labels_band_hist: the label maps, geometry and ground truth of launch_labels_hist -> the same counts, ADDED to hist[b * ncls * ncls + gt * ncls +
+// pred] with b = the number of widths[i] <= d of the ground truth at cap = widths[nwidths - 1] (1 .. 4 strictly ascending host ints in 1 .. 16): (nwidths +
+// 1) * ncls * ncls words, utils/image.py band_hist_host.  Device pointers but `widths`; the kernels only read their inputs
+hipError_t launch_boundary_distance(const unsigned char* maps, int n, int h, int w, size_t pitch, int cap, unsigned char* dst, size_t dst_pitch, hipStream_t st);
+hipError_t launch_labels_band_hist(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, const unsigned char* gt, int h, int w,
+                                   size_t gt_pitch, int ncls, const int* widths, int nwidths, unsigned long long* hist, hipStream_t st);
 
 struct PoolParams {
     const float* x; float* y;

@@ -213,6 +213,15 @@ def run_clip(version, cfg, arg_params, aux_params, frames_bgr, interval, want_lo
     return outs
 
 
+def _trimap_widths(text):
+    """--trimap: '1,2,4,8' -> (1, 2, 4, 8)"""
+    from .utils.image import band_widths
+    try:
+        return band_widths(int(v) for v in text.split(','))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Accel demo (MI355X)')
     ap.add_argument('--version', default='18')
@@ -263,6 +272,10 @@ def main(argv=None):
                     help='with --finish-on-gpu: per frame, the three largest classes with their share of the frame and their box, and from the '
                          'second frame of a clip on the label churn against the previous frame -- counted on the GPU at the source size, a few '
                          'hundred bytes per frame instead of the label map.  With --interpolate the labels are those of the interpolated scores')
+    ap.add_argument('--trimap', type=_trimap_widths, default=None, metavar='W1,W2,..',
+                    help='with --finish-on-gpu: 1 to 4 ascending band widths in pixels (1 .. 16), such as 1,2,4,8: at the end of the run, one line '
+                         'per width with the mIoU restricted to the pixels closer than that to a ground-truth boundary -- where feature '
+                         'propagation costs accuracy first -- counted on the GPU with the mIoU itself (honours --interpolate)')
     ap.add_argument('--adaptive-key', dest='adaptive_key', type=float, default=None, metavar='SHARE',
                     help='content-adaptive key frames: a frame becomes a key frame when more than SHARE (0 .. 1) of its cells changed against '
                          'the last key frame, measured on the GPU where the frame is; --interval is then the LONGEST distance between key '
@@ -273,6 +286,8 @@ def main(argv=None):
     ap.add_argument('--scales', default='', help='TARGETxMAX: resize target for the short side and limit for the long side '
                                                  '(overrides SCALES of the configuration, also the one --synthetic sets)')
     args = ap.parse_args(argv)
+    if args.trimap and not args.finish_on_gpu:
+        ap.error("--trimap needs --finish-on-gpu: the bands are counted on the GPU")
     version, interv, num_ex = str(args.version), args.interval, args.num_ex
     if version not in ['18', '34', '50', '101', 'dff']:
         raise ValueError("Invalid Accel version '%s' - must be one of Accel-{18,34,50,101} (or 'dff')" % version)
@@ -333,6 +348,7 @@ def main(argv=None):
         g = resize_geometry(H, W, config.SCALES[0][0], config.SCALES[0][1], config.network.IMAGE_STRIDE)
         source = dict(out_h=g[1], out_w=g[2], h=H, w=W)
         evaluator, hist_before = results.Evaluator(num_classes), np.zeros((num_classes, num_classes), np.int64)
+        trimap = results.TrimapEvaluator(num_classes, args.trimap) if args.trimap else None
     if args.raw_frames:       # the size the graphs are bound at: the frame after resize + padding
         from .utils.image import resize_geometry
         H, W = resize_geometry(H, W, config.SCALES[0][0], config.SCALES[0][1], config.network.IMAGE_STRIDE)[3:]
@@ -432,6 +448,8 @@ def main(argv=None):
                     evaluator.add(lab, label, like=source)
                 hist = evaluator.hist()
                 curr_hist, hist_before = hist - hist_before, hist
+                if trimap is not None:
+                    trimap.add(lg if args.interpolate else lab, label, like=source, interpolate=args.interpolate)
             else:
                 curr_hist = fast_hist(pred.flatten(), label.flatten(), num_classes)
                 hist += curr_hist
@@ -441,6 +459,9 @@ def main(argv=None):
         ious = per_class_iu(hist) * 100
         print(' '.join('{:.03f}'.format(i) for i in ious))
         print('===> final mIoU {mIoU:.3f}'.format(mIoU=round(np.nanmean(ious), 2)))
+        if args.trimap:
+            for width, miou in zip(trimap.widths, trimap.miou()):
+                print('trimap {:2d} px: mIoU {:.2f}'.format(width, miou * 100))
     print('{:.2f} frames/s'.format(count / time_sum))
     print('done')
 

@@ -119,6 +119,11 @@ def _declare(lib):
         "accel_model_labels_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
         "accel_model_scores_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
         "accel_model_labels_forget": [vp],
+        "accel_boundary_distance": [vp, vp, i, i, i, sz, i, vp, sz],
+        "accel_labels_band_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, c.POINTER(c.c_int), i, vp],
+        "accel_model_band_hist_add": [vp, vp, i, i, i, sz, i, i, i, c.POINTER(c.c_int), i, i],
+        "accel_model_scores_band_hist_add": [vp, vp, i, i, i, sz, i, i, i, c.POINTER(c.c_int), i, i],
+        "accel_model_band_hist_read": [vp, vp, i, i, i],
         "accel_labels_overlay_yuv": [vp, vp, i, i, i, i, i, c.POINTER(YUVLayout), vp, i, vp, vp],
         "accel_model_labels_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
         "accel_model_scores_overlay_yuv": [vp, i, i, i, c.POINTER(YUVLayout), vp, i, vp, i, vp, i],
@@ -290,6 +295,12 @@ def _u8_maps(maps, width=None, what="labels"):
     if a.ndim != 3:
         raise ValueError("%s must be n x h x w uint8, got shape %s" % (what, a.shape))
     return a, a.shape[0], a.shape[1], a.shape[2] if width is None else int(width), a.shape[2]
+
+
+def _widths(widths):
+    """the widths of a trimap as the C ABI takes them: an array of ints (the library checks their values)"""
+    ws = [int(v) for v in widths]
+    return (ctypes.c_int * len(ws))(*ws)
 
 
 def _palette(palette):
@@ -549,6 +560,28 @@ class Context(object):
             raise ValueError("%d label maps but %d ground-truth maps" % (n, gn))
         hist = np.zeros((int(ncls), int(ncls)), np.uint64) if hist is None else np.ascontiguousarray(hist, dtype=np.uint64).copy()
         check(lib().accel_labels_hist(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), _fp(g), h, w, pitch, int(ncls), _fp(hist)))
+        return hist
+
+    def boundary_distance(self, maps, cap, width=None, out=None):
+        """accel_boundary_distance: n x h x w uint8 maps (or n x h x pitch bytes with `width`) -> n x h x w uint8, the Chebyshev distance of every
+        pixel to the nearest pixel with a differing 4-neighbour, capped at `cap` in 1 .. 16 (utils.image.boundary_distance_host); `out`: n x h x pitch
+        bytes to write the rows into instead"""
+        g, n, h, w, pitch = _u8_maps(maps, width, "maps")
+        out, out_pitch = _result_rows(out, n, h, w, 1)
+        check(lib().accel_boundary_distance(self.handle, _fp(g), n, h, w, pitch, int(cap), _fp(out), out_pitch))
+        return out
+
+    def labels_band_hist(self, labels, out_h, out_w, gt, ncls, widths, width=None, hist=None):
+        """accel_labels_band_hist: the confusion matrix of labels_hist split into buckets of the distance to the boundaries of `gt`: uint64
+        (len(widths) + 1) x ncls x ncls (utils.image.band_hist_host), added to `hist` when one is given"""
+        a, n, H, W, _ = _u8_maps(labels)
+        g, gn, h, w, pitch = _u8_maps(gt, width, "gt")
+        if gn != n:
+            raise ValueError("%d label maps but %d ground-truth maps" % (n, gn))
+        ws = _widths(widths)
+        shape = (len(ws) + 1, int(ncls), int(ncls))
+        hist = np.zeros(shape, np.uint64) if hist is None else np.ascontiguousarray(hist, dtype=np.uint64).reshape(shape).copy()
+        check(lib().accel_labels_band_hist(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), _fp(g), h, w, pitch, int(ncls), ws, len(ws), _fp(hist)))
         return hist
 
     def labels_colour(self, labels, out_h, out_w, h, w, palette, frames=None, alpha=256, rgb=True, width=None, out=None):
@@ -1016,6 +1049,32 @@ class Model(object):
         """accel_model_hist_read: the accumulator as uint64 ncls x ncls (rows gt, columns prediction); clear=True zeroes it"""
         out = np.zeros((int(ncls), int(ncls)), np.uint64)
         check(lib().accel_model_hist_read(self.handle, _fp(out), int(ncls), int(bool(clear))))
+        return out
+
+    # ---- trimap evaluation: an accumulator of its own, (len(widths) + 1) x ncls x ncls buckets ------------------------------------------
+    def band_hist_add(self, gt, out_h, out_w, ncls, widths, width=None):
+        """accel_model_band_hist_add: add the confusion matrix of `labels` against host ground truth (as hist_add takes it), split into buckets of
+        the distance to the ground truth's boundaries, to the model's band accumulator (enqueued: no host wait beyond the upload of gt)"""
+        g, n, h, w, pitch = _u8_maps(gt, width, "gt")
+        ws = _widths(widths)
+        check(lib().accel_model_band_hist_add(self.handle, _fp(g), n, h, w, pitch, int(out_h), int(out_w), int(ncls), ws, len(ws), 0))
+
+    def band_hist_add_device(self, dev_ptr, n, h, w, pitch, out_h, out_w, ncls, widths):
+        """the same against ground truth in caller-owned HBM: n x h rows, `pitch` bytes apart"""
+        ws = _widths(widths)
+        check(lib().accel_model_band_hist_add(self.handle, ctypes.c_void_p(dev_ptr), int(n), int(h), int(w), int(pitch), int(out_h), int(out_w), int(ncls),
+                                              ws, len(ws), 1))
+
+    def scores_band_hist_add(self, gt, out_h, out_w, ncls, widths, width=None):
+        """accel_model_scores_band_hist_add: band_hist_add with the labels of the interpolated scores: the same accumulator, the same rule"""
+        g, n, h, w, pitch = _u8_maps(gt, width, "gt")
+        ws = _widths(widths)
+        check(lib().accel_model_scores_band_hist_add(self.handle, _fp(g), n, h, w, pitch, int(out_h), int(out_w), int(ncls), ws, len(ws), 0))
+
+    def band_hist_read(self, ncls, nwidths, clear=False):
+        """accel_model_band_hist_read: the band accumulator as uint64 (nwidths + 1) x ncls x ncls buckets; clear=True zeroes it"""
+        out = np.zeros((int(nwidths) + 1, int(ncls), int(ncls)), np.uint64)
+        check(lib().accel_model_band_hist_read(self.handle, _fp(out), int(ncls), int(nwidths), int(bool(clear))))
         return out
 
     def _colour(self, fn, n, out_h, out_w, h, w, palette, frames, alpha, rgb, width, out):

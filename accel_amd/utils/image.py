@@ -924,3 +924,94 @@ def summary_churn(trans):
     trace = t[..., ::ncls + 1].sum(axis=-1)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(total > 0, 1.0 - trace / total, np.nan)
+
+
+# ---- trimap evaluation: the confusion matrix in bands around the ground truth's boundaries (csrc/labels_band.hip restates it bit for bit) --------
+def _u8_batch(maps, what):
+    a = np.asarray(maps, np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("%s must be [n x] h x w uint8, got shape %s" % (what, a.shape))
+    return a
+
+
+def band_widths(widths):
+    """the widths of a trimap as a tuple of ints: 1 to 4 strictly ascending values in 1 .. 16, or ValueError"""
+    try:
+        ws = tuple(int(v) for v in widths)
+    except (TypeError, ValueError):
+        raise ValueError("widths must be a sequence of 1 to 4 integers, got %r" % (widths,))
+    if not 1 <= len(ws) <= 4:
+        raise ValueError("widths holds %d values, must hold 1 .. 4" % len(ws))
+    if any(not 1 <= v <= 16 for v in ws):
+        raise ValueError("widths = %s, every width must be in 1 .. 16" % (ws,))
+    if any(b <= a for a, b in zip(ws, ws[1:])):
+        raise ValueError("widths = %s, must be strictly ascending" % (ws,))
+    return ws
+
+
+def boundary_edges_host(maps):
+    """[n x] h x w uint8 -> n x h x w bool: the pixels with a 4-neighbour INSIDE the frame that holds another byte.  Raw bytes: the border between a
+    class and an ignored id is an edge.  The frames of a batch are independent"""
+    g = _u8_batch(maps, "maps")
+    e = np.zeros(g.shape, bool)
+    dy, dx = g[:, 1:, :] != g[:, :-1, :], g[:, :, 1:] != g[:, :, :-1]
+    e[:, 1:, :] |= dy
+    e[:, :-1, :] |= dy
+    e[:, :, 1:] |= dx
+    e[:, :, :-1] |= dx
+    return e
+
+
+def boundary_distance_host(maps, cap):
+    """The specification of accel_boundary_distance: n x h x w uint8,
+        d(y, x) = min(cap, min over edge pixels (y', x') of max(|y - y'|, |x - x'|))        (boundary_edges_host; cap in 1 .. 16)
+    the Chebyshev distance to the nearest edge pixel: 0 on one, cap where none lies closer and where the map has no edge.  Written as cap - 1
+    rounds of 3 x 3 dilation of the edge set: a pixel first reached in round r has d = r."""
+    cap = int(cap)
+    if not 1 <= cap <= 16:
+        raise ValueError("cap = %d, must be in 1 .. 16" % cap)
+    reached = boundary_edges_host(maps)
+    d = np.where(reached, 0, cap).astype(np.uint8)
+    for r in range(1, cap):
+        grown = reached.copy()
+        grown[:, 1:, :] |= reached[:, :-1, :]
+        grown[:, :-1, :] |= reached[:, 1:, :]
+        rows = grown.copy()
+        rows[:, :, 1:] |= grown[:, :, :-1]
+        rows[:, :, :-1] |= grown[:, :, 1:]
+        d[rows & ~reached] = r
+        reached = rows
+    return d
+
+
+def band_buckets_host(d, widths):
+    """the bucket of every distance: the number of widths[i] <= d, so that bucket k < K holds widths[k - 1] <= d < widths[k] and bucket K the rest"""
+    ws = band_widths(widths)
+    return np.searchsorted(np.asarray(ws, np.int64), np.asarray(d, np.int64), side="right")
+
+
+def band_hist_host(labels, out_h, out_w, gt, ncls, widths):
+    """The specification of accel_labels_band_hist: (K + 1) x ncls x ncls uint64 BUCKETS.  `labels` is [n x] H x W uint8 with the valid region
+    out_h x out_w, `gt` [n x] h x w uint8; with pred = labels_to_source_host(labels, out_h, out_w, h, w) and d = boundary_distance_host(gt, widths[-1]),
+    a source pixel adds 1 to [bucket(d)][gt][pred] when gt < ncls and pred < ncls.  The band of width widths[k] is the sum of the buckets 0 .. k
+    (band_cumulative); the sum of all K + 1 is the whole-frame confusion matrix."""
+    ws = band_widths(widths)
+    ncls = int(ncls)
+    if not 1 <= ncls <= 32:
+        raise ValueError("ncls = %d, must be in 1 .. 32" % ncls)
+    g = _u8_batch(gt, "gt")
+    a = _u8_batch(labels, "labels")
+    if a.shape[0] != g.shape[0]:
+        raise ValueError("%d label maps but %d ground-truth maps" % (a.shape[0], g.shape[0]))
+    pred = labels_to_source_host(a, out_h, out_w, g.shape[1], g.shape[2])
+    bucket = band_buckets_host(boundary_distance_host(g, ws[-1]), ws)
+    ok = (g < ncls) & (pred < ncls)
+    at = (bucket[ok] * ncls + g[ok].astype(np.int64)) * ncls + pred[ok].astype(np.int64)
+    return np.bincount(at, minlength=(len(ws) + 1) * ncls * ncls).astype(np.uint64).reshape(len(ws) + 1, ncls, ncls)
+
+
+def band_cumulative(buckets):
+    """(K + 1) x ncls x ncls buckets -> the same shape, int64: [k] is the band of width widths[k] (the sum of the buckets 0 .. k), [K] the whole frame"""
+    return np.cumsum(np.asarray(buckets).astype(np.int64), axis=0)

@@ -553,6 +553,44 @@ int accel_model_scores_summary(accel_model* m, int n, int out_h, int out_w, int 
                                uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared);
 int accel_model_labels_forget(accel_model* m);
 
+/* ---- finished frames: trimap evaluation, the confusion matrix in bands around the ground truth's boundaries ------------
+ * Whole-frame mIoU is dominated by interior pixels; what feature propagation costs sits at object boundaries.  For a
+ * ground-truth map g (h x w uint8, rows `gt_pitch` apart; the frames of a batch are independent):
+ *   edge pixel    one of its 4-neighbours INSIDE the frame holds another byte (raw bytes: the border between a class and an
+ *                 ignored id is an edge; a neighbour outside the frame is never different)
+ *   d(y, x)       min(cap, min over edge pixels (y', x') of max(|y - y'|, |x - x'|)): the Chebyshev distance to the nearest
+ *                 edge pixel, 0 on one, cap where none lies closer and where the map has no edge
+ *   widths        1 .. 4 strictly ascending ints in 1 .. 16; cap = the last one.  Bucket b < nwidths holds the pixels with
+ *                 widths[b - 1] <= d < widths[b] (0 for b = 0), bucket nwidths the rest
+ *   counting      a source pixel adds 1 to hist[b][gt * ncls + pred] when gt < ncls and pred < ncls, pred by the nearest rule
+ *                 of accel_labels_hist: (nwidths + 1) * ncls * ncls uint64.  The band of width widths[b] is the sum of the
+ *                 buckets 0 .. b (taken by the caller); the sum of ALL buckets is the matrix accel_labels_hist gives
+ * (accel_amd/utils/image.py boundary_distance_host, band_hist_host; csrc/labels_band.hip).  Integer arithmetic: exact.
+ * Argument errors (a NULL pointer, nwidths outside 1 .. 4, a width or cap outside 1 .. 16, widths not strictly ascending,
+ * ncls outside 1 .. 32, a size < 1 or > 32768, out_h > H, out_w > W, a pitch smaller than a row, a model without `labels` /
+ * `logits` of n frames, other ncls or widths than the accumulator's since its last clear) return ACCEL_ERR_ARG before
+ * anything is enqueued, with a message that names the argument.
+ *   accel_boundary_distance       host maps (n x h rows, `pitch` apart) in, d out as bytes (rows `dst_pitch` apart; bytes
+ *                                 between rows are not written).  Any label maps: ground truth or fetched predictions;
+ *                                 d == 0 is the outline a viewer draws.  Stateless
+ *   accel_labels_band_hist        operator level, host bytes: the buckets are ADDED to `hist`.  Stateless
+ *   accel_model_band_hist_add     the same on the model's `labels` buffer, enqueued on the context stream (gt_on_device as
+ *                                 in accel_model_hist_add), into an accumulator of the model's own that is SEPARATE from
+ *                                 the one of accel_model_hist_add: it remembers ncls and widths and refuses other values
+ *                                 until it has been cleared; freed with the model
+ *   accel_model_scores_band_hist_add   with the labels of the bilinearly INTERPOLATED scores (accel_model_scores_labels),
+ *                                 through the model's n x h x w scratch: the same accumulator
+ *   accel_model_band_hist_read    waits for the stream and copies (nwidths + 1) * ncls * ncls words to the host (zeros
+ *                                 when nothing was added since the last clear); clear = 1 zeroes the accumulator */
+int accel_boundary_distance(accel_ctx* ctx, const uint8_t* maps, int n, int h, int w, size_t pitch, int cap, uint8_t* dst, size_t dst_pitch);
+int accel_labels_band_hist(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w,
+                           const uint8_t* gt, int h, int w, size_t gt_pitch, int ncls, const int* widths, int nwidths, uint64_t* hist);
+int accel_model_band_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                              const int* widths, int nwidths, int gt_on_device);
+int accel_model_scores_band_hist_add(accel_model* m, const uint8_t* gt, int n, int h, int w, size_t gt_pitch, int out_h, int out_w, int ncls,
+                                     const int* widths, int nwidths, int gt_on_device);
+int accel_model_band_hist_read(accel_model* m, uint64_t* out, int ncls, int nwidths, int clear);
+
 /* ---- finished frames: the overlay in the frame's own format ------------------------------------------------------------
  * The label map blended over NV12, I420 / YV12, P010 or YUY2 frames and written as the same format in the same layout
  * (csrc/overlay_yuv.hip): what an encoder, a compositor or a capture-card output takes, with no BGR picture in between.
