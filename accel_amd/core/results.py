@@ -8,6 +8,9 @@ source size and takes the argmax there (csrc/scores_labels.hip behind accel_mode
 hands back the frames' own format (csrc/overlay_yuv.hip behind accel_model_labels_overlay_yuv / _scores_overlay_yuv).  `summary` says what
 is in the frame, where, and whether it just changed: per-class areas, coordinate sums and boxes, and the class transitions against the
 previous frame, which is kept in HBM (csrc/labels_summary.hip behind accel_model_labels_summary / _scores_summary / _labels_forget).
+`components` says how many objects of every class there are and where each one is: the connected components of the label map with their
+area, box, first pixel and coordinate sums, in raster order, and the object index per pixel if asked (csrc/labels_components.hip behind
+accel_model_labels_components / _scores_components).
 `TrimapEvaluator` counts the confusion matrix in bands around the ground truth's boundaries, where propagated features are damaged first, and
 `boundary_distance` gives the distance map itself (csrc/labels_band.hip behind accel_model_band_hist_add / _scores_band_hist_add /
 _band_hist_read and accel_boundary_distance).
@@ -25,6 +28,7 @@ import numpy as np
 
 from .. import runtime
 from ..utils.image import summary_centroids, summary_churn  # noqa: F401  (re-exported: the host helpers of `summary`)
+from ..utils.image import components_centroids, components_of  # noqa: F401  (re-exported: the host helpers of `components`)
 
 
 def _geometry(handle, like, hw=None, scores=False):
@@ -167,6 +171,25 @@ def summary(handle, like, ncls=19, track=False, interpolate=False, box=True):
     n, out_h, out_w, h, w = _geometry(handle, like, scores=bool(interpolate))
     run = m.scores_summary if interpolate else m.labels_summary
     return Summary(*run(n, out_h, out_w, h, w, int(ncls), track=bool(track), stats=True, box=bool(box)))
+
+
+Components = collections.namedtuple("Components", "count comp sums ids")
+
+
+def components(handle, like, ncls=19, connectivity=8, min_area=1, max_components=1024, ids=False, interpolate=False):
+    """The objects of every class, from the labels of `handle` at the source frames' size without fetching them: Components(count, comp, sums,
+    ids) of the connected components of equal labels < ncls (4- or 8-connected; ids >= ncls are background and separate components) with at
+    least min_area pixels, in raster order of their first pixel -- count n int32 = their number per frame (the full number, also above
+    max_components), comp n x max_components x 8 int32 = (class, area, x0, y0, x1, y1, ax, ay) with the inclusive box and the first pixel, -1 in
+    the unused records, sums n x max_components x 2 uint64 = (sum_x, sum_y) (components_centroids gives the centroids, components_of the
+    trimmed records of one frame), ids n x h x w int32 = the record index per source pixel or -1 (None with ids=False)
+    (utils.image.labels_components_host, on the GPU: csrc/labels_components.hip).  interpolate=True: `handle` is the LOGITS handle, the labels
+    are those of labels_at_source(handle, like, interpolate=True) and ncls must be the class count of the scores."""
+    m = _model(handle, "logits" if interpolate else "labels")
+    n, out_h, out_w, h, w = _geometry(handle, like, scores=bool(interpolate))
+    run = m.scores_components if interpolate else m.labels_components
+    return Components(*run(n, out_h, out_w, h, w, int(ncls), connectivity=int(connectivity), min_area=int(min_area),
+                           max_components=int(max_components), comp=True, sums=True, ids=bool(ids)))
 
 
 def forget(handle):

@@ -1461,6 +1461,159 @@ extern "C" int accel_model_labels_forget(accel_model* m)
     return 0;
 }
 
+// ---- connected components of finished frames: objects per class (labels_components.hip) -------------------------------------------------------------
+// What the three entry points share beyond the geometry, checked before anything is enqueued: every message names the argument at fault.
+static int components_args(const char* fn, int n, int w, int ncls, int connectivity, int min_area, int max_components, const int32_t* count,
+                           const int32_t* ids, size_t ids_pitch)
+{
+    if (n > 32768) return fail(ACCEL_ERR_ARG, "%s: n = %d, must be in 1 .. 32768", fn, n);
+    if (int rc = ncls_arg(fn, ncls)) return rc;
+    if (connectivity != 4 && connectivity != 8) return fail(ACCEL_ERR_ARG, "%s: connectivity = %d, must be 4 or 8", fn, connectivity);
+    if (min_area < 1) return fail(ACCEL_ERR_ARG, "%s: min_area = %d, must be >= 1", fn, min_area);
+    if (max_components < 1 || max_components > 65536)
+        return fail(ACCEL_ERR_ARG, "%s: max_components = %d, must be in 1 .. 65536", fn, max_components);
+    if (!count) return fail(ACCEL_ERR_ARG, "%s: count is NULL", fn);
+    if (ids) {
+        if (int rc = pitch_arg(fn, "ids_pitch", ids_pitch, w, 4)) return rc;
+        if (ids_pitch % 4) return fail(ACCEL_ERR_ARG, "%s: ids_pitch = %zu bytes, must be a multiple of 4", fn, ids_pitch);
+    }
+    return 0;
+}
+
+// the device side of a components call whose results go to the host: count (n words), comp (n x max_components x 8), sums (n x max_components x 2
+// words of 8 bytes), ids (n * h tight rows of w words), each part 256-byte aligned
+struct ComponentsStage : Carved {
+    size_t count = 0, comp = 0, sums = 0, ids = 0, nb, cb, sb, ib;
+    ComponentsStage(int n, int h, int w, int max_components, bool c, bool s, bool i)
+        : nb((size_t)n * sizeof(int32_t)), cb((size_t)n * max_components * 8 * sizeof(int32_t)), sb((size_t)n * max_components * 2 * sizeof(uint64_t)),
+          ib((size_t)n * h * w * sizeof(int32_t))
+    {
+        count = take(nb);
+        if (c) comp = take(cb);
+        if (s) sums = take(sb);
+        if (i) ids = take(ib);
+    }
+};
+
+// the scratch of launch_labels_components for n frames of h x w, carved out of one allocation: parent, area, blocks
+struct ComponentsScratch : Carved {
+    size_t parent, area, blocks;
+    ComponentsScratch(int n, int h, int w)
+    {
+        parent = take((size_t)n * h * w * sizeof(int32_t));
+        area = take((size_t)n * h * w * sizeof(int32_t));
+        blocks = take((size_t)n * labels_components_chunks(h, w) * sizeof(int32_t));
+    }
+};
+
+struct ComponentsOut { int32_t* count; int32_t* comp; uint64_t* sums; int32_t* ids; size_t ids_pitch; };
+
+static hipError_t components_launch(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, int connectivity,
+                                    int min_area, int max_components, unsigned char* scratch, const ComponentsOut& o, hipStream_t st)
+{
+    const ComponentsScratch cs(n, h, w);
+    return launch_labels_components(labels, n, H, W, out_h, out_w, h, w, ncls, connectivity, min_area, max_components,
+                                    reinterpret_cast<int*>(scratch + cs.parent), reinterpret_cast<int*>(scratch + cs.area),
+                                    reinterpret_cast<int*>(scratch + cs.blocks), o.count, o.comp, reinterpret_cast<unsigned long long*>(o.sums), o.ids,
+                                    o.ids_pitch, st);
+}
+
+// the components of `labels` into the stage at `base`, the results copied to the host; the caller waits
+static int components_to_host(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, int connectivity,
+                              int min_area, int max_components, unsigned char* scratch, unsigned char* base, const ComponentsStage& cs,
+                              const ComponentsOut& host, hipStream_t st)
+{
+    const ComponentsOut dev = {reinterpret_cast<int32_t*>(base + cs.count), host.comp ? reinterpret_cast<int32_t*>(base + cs.comp) : nullptr,
+                               host.sums ? reinterpret_cast<uint64_t*>(base + cs.sums) : nullptr,
+                               host.ids ? reinterpret_cast<int32_t*>(base + cs.ids) : nullptr, (size_t)4 * w};
+    HIP_TRY(components_launch(labels, n, H, W, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, scratch, dev, st));
+    HIP_TRY(hipMemcpyAsync(host.count, dev.count, cs.nb, hipMemcpyDeviceToHost, st));
+    if (host.comp) HIP_TRY(hipMemcpyAsync(host.comp, dev.comp, cs.cb, hipMemcpyDeviceToHost, st));
+    if (host.sums) HIP_TRY(hipMemcpyAsync(host.sums, dev.sums, cs.sb, hipMemcpyDeviceToHost, st));
+    if (host.ids) HIP_TRY(rows_to_host(host.ids, host.ids_pitch, dev.ids, (size_t)4 * w, (size_t)n * h, st));
+    return 0;
+}
+
+extern "C" int accel_labels_components(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls,
+                                       int connectivity, int min_area, int max_components, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                                       size_t ids_pitch)
+{
+    const char* fn = "accel_labels_components";
+    if (!ctx) return fail(ACCEL_ERR_ARG, "%s: ctx is NULL", fn);
+    if (!labels) return fail(ACCEL_ERR_ARG, "%s: labels is NULL", fn);
+    if (int rc = results_args(fn, n, H, W, out_h, out_w, h, w)) return rc;
+    if (int rc = components_args(fn, n, w, ncls, connectivity, min_area, max_components, count, ids, ids_pitch)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevTemps t;
+    const ComponentsStage cs(n, h, w, max_components, comp, sums, ids);
+    const ComponentsScratch sc(n, h, w);
+    const unsigned char* l = static_cast<const unsigned char*>(t.upload(labels, (size_t)n * H * W));
+    unsigned char* scratch = static_cast<unsigned char*>(t.get(sc.bytes));
+    unsigned char* base = static_cast<unsigned char*>(t.get(cs.bytes));
+    if (!l || !scratch || !base) return fail(ACCEL_ERR_HIP, "%s: device allocation or upload failed", fn);
+    const ComponentsOut host = {count, comp, sums, ids, ids_pitch};
+    if (int rc = components_to_host(l, n, H, W, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, scratch, base, cs, host, ctx->stream))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// what the two model-level forms share: the components of the n maps of `src` at the source size
+static int model_components(const char* fn, accel_model* m, LabelSource::Kind kind, int n, int out_h, int out_w, int h, int w, int ncls, int connectivity,
+                            int min_area, int max_components, int dst_on_device, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                            size_t ids_pitch)
+{
+    if (!m) return fail(ACCEL_ERR_ARG, "%s: m is NULL", fn);
+    LabelSource src(m, kind);
+    if (int rc = src.find(fn, n)) return rc;
+    if (int rc = src.geometry(fn, out_h, out_w, h, w)) return rc;
+    if (int rc = components_args(fn, n, w, ncls, connectivity, min_area, max_components, count, ids, ids_pitch)) return rc;
+    if (kind == LabelSource::INTERPOLATED && ncls != src.ncls)
+        return fail(ACCEL_ERR_ARG, "%s: ncls = %d, the scores have %d classes", fn, ncls, src.ncls);
+    if (dst_on_device) {
+        if (reinterpret_cast<uintptr_t>(count) % 4) return fail(ACCEL_ERR_ARG, "%s: count = %p, device words must be 4-byte aligned", fn, (void*)count);
+        if (reinterpret_cast<uintptr_t>(comp) % 4) return fail(ACCEL_ERR_ARG, "%s: comp = %p, device words must be 4-byte aligned", fn, (void*)comp);
+        if (reinterpret_cast<uintptr_t>(sums) % 8) return fail(ACCEL_ERR_ARG, "%s: sums = %p, device words must be 8-byte aligned", fn, (void*)sums);
+        if (reinterpret_cast<uintptr_t>(ids) % 4) return fail(ACCEL_ERR_ARG, "%s: ids = %p, device words must be 4-byte aligned", fn, (void*)ids);
+    }
+    hipStream_t st = m->ctx->stream;
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    if (int rc = src.reserve()) return rc;
+    const ComponentsScratch sc(n, h, w);
+    if (int rc = m->components.reserve(m->ctx->device, sc.bytes)) return rc;
+    const ComponentsOut out = {count, comp, sums, ids, ids_pitch};
+    if (dst_on_device) {
+        HIP_TRY(src.enqueue(st));
+        HIP_TRY(components_launch(src.maps, n, src.H, src.W, src.out_h, src.out_w, h, w, ncls, connectivity, min_area, max_components,
+                                  m->components.ptr, out, st));
+        return 0;
+    }
+    const ComponentsStage cs(n, h, w, max_components, comp, sums, ids);
+    if (int rc = m->stage_out.reserve(m->ctx->device, cs.bytes)) return rc;
+    HIP_TRY(src.enqueue(st));
+    if (int rc = components_to_host(src.maps, n, src.H, src.W, src.out_h, src.out_w, h, w, ncls, connectivity, min_area, max_components,
+                                    m->components.ptr, m->stage_out.ptr, cs, out, st))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int accel_model_labels_components(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int connectivity, int min_area,
+                                             int max_components, int dst_on_device, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                                             size_t ids_pitch)
+{
+    return model_components("accel_model_labels_components", m, LabelSource::NEAREST, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components,
+                            dst_on_device, count, comp, sums, ids, ids_pitch);
+}
+
+extern "C" int accel_model_scores_components(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int connectivity, int min_area,
+                                             int max_components, int dst_on_device, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                                             size_t ids_pitch)
+{
+    return model_components("accel_model_scores_components", m, LabelSource::INTERPOLATED, n, out_h, out_w, h, w, ncls, connectivity, min_area,
+                            max_components, dst_on_device, count, comp, sums, ids, ids_pitch);
+}
+
 // ---- trimap evaluation: the distance to the ground truth's boundaries and the confusion matrix per band of it (labels_band.hip) ---------------------
 static int widths_arg(const char* fn, const int* widths, int nwidths)
 {

@@ -132,6 +132,9 @@ struct accel_model {
         int n = 0, h = 0, w = 0, ncls = 0;
     };
     KeptLabels kept_labels;
+    // accel_model_labels_components / _scores_components: the scratch of labels_components.hip, one allocation carved into the parent and the
+    // area / slot word per source pixel and the counts per chunk (accel_io.cpp ComponentsScratch); kept for the next frame, freed with the model
+    DevScratch components;
     // which buffer holds the current propagated feature: 0 = `feat`, 1 = `feat_b` (non-key graphs may be bound as a pair of
     // plans `cur` / `cur_b` that ping-pong between the two instead of copying the warped feature back; whoever wrote last)
     int feat_slot = 0;

@@ -218,6 +218,16 @@ hipError_t launch_frame_change(const float* img, const int* sig_key, int n, int 
 hipError_t launch_labels_summary(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, const unsigned char* prev,
                                  size_t prev_pitch, unsigned long long* stats, int* box, unsigned long long* trans, unsigned char* kept, size_t kept_pitch,
                                  hipStream_t st);
+// connected components of finished frames (labels_components.hip): the label maps and geometry of launch_labels_source -> per frame the components of
+// equal labels < ncls (<= 32) under `connectivity` (4 or 8) with area >= min_area, in ascending order of their first pixel in raster order: count[f] =
+// their number (also above max_components), comp[f][i] = (class, area, x0, y0, x1, y1, ax, ay) int32 and sums[f][i] = (sum_x, sum_y) uint64 of the
+// first max_components of them (-1 / 0 in the records after), ids = per source pixel the record index or -1 (rows ids_pitch bytes apart):
+// utils/image.py labels_components_host.  Scratch: parent and area n * h * w int32 each, blocks n * labels_components_chunks(h, w) int32.  comp, sums
+// and ids may be null.  Device pointers; the kernels only read `labels`
+size_t labels_components_chunks(int h, int w);
+hipError_t launch_labels_components(const unsigned char* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls, int connectivity,
+                                    int min_area, int max_components, int* parent, int* area, int* blocks, int* count, int* comp,
+                                    unsigned long long* sums, int* ids, size_t ids_pitch, hipStream_t st);
 // trimap evaluation (labels_band.hip).  launch_boundary_distance: n maps of h x w bytes (rows `pitch` apart) -> d = min(cap, Chebyshev distance to the
 // nearest pixel with a differing 4-neighbour inside its frame), 1 <= cap <= 16, as bytes (rows `dst_pitch` apart): utils/image.py boundary_distance_host.
 // launch_labels_band_hist: the label maps, geometry and ground truth of launch_labels_hist -> the same counts, ADDED to hist[b * ncls * ncls + gt * ncls +

@@ -272,6 +272,11 @@ def main(argv=None):
                     help='with --finish-on-gpu: per frame, the three largest classes with their share of the frame and their box, and from the '
                          'second frame of a clip on the label churn against the previous frame -- counted on the GPU at the source size, a few '
                          'hundred bytes per frame instead of the label map.  With --interpolate the labels are those of the interpolated scores')
+    ap.add_argument('--components', type=int, nargs='?', const=64, default=None, metavar='MIN_AREA',
+                    help='with --finish-on-gpu: per frame, the number of objects of every class that has any -- the connected components of the '
+                         'labels at the source size with at least MIN_AREA pixels (default 64), found on the GPU -- and the class, box and area '
+                         'of the largest one; "(truncated)" when there are more objects than records.  With --interpolate the labels are those '
+                         'of the interpolated scores')
     ap.add_argument('--trimap', type=_trimap_widths, default=None, metavar='W1,W2,..',
                     help='with --finish-on-gpu: 1 to 4 ascending band widths in pixels (1 .. 16), such as 1,2,4,8: at the end of the run, one line '
                          'per width with the mIoU restricted to the pixels closer than that to a ground-truth boundary -- where feature '
@@ -301,6 +306,8 @@ def main(argv=None):
         raise ValueError("--interpolate needs --finish-on-gpu")
     if args.summary and not args.finish_on_gpu:
         raise ValueError("--summary needs --finish-on-gpu")
+    if args.components is not None and not args.finish_on_gpu:
+        raise ValueError("--components needs --finish-on-gpu")
     if args.nv12 and args.yuv:
         raise ValueError("--nv12 and --yuv are mutually exclusive: the frames are fed in one format")
     if args.overlay_yuv and not (args.finish_on_gpu and (args.nv12 or args.yuv)):
@@ -416,6 +423,18 @@ def main(argv=None):
             if s.trans is not None:
                 line += ' churn {:.3f}'.format(float(results.summary_churn(s.trans)[0]))
             print('summary ' + line)
+        if args.components is not None:       # after the clock: how many objects of every class, and the largest one -- a few KB per frame
+            c = results.components(lg if args.interpolate else lab, source, ncls=num_classes, min_area=args.components,
+                                   interpolate=args.interpolate)
+            rec, _ = results.components_of(c, 0)
+            per_class = np.bincount(rec[:, 0], minlength=num_classes)
+            line = ' '.join('{}:{}'.format(k, per_class[k]) for k in range(num_classes) if per_class[k])
+            if len(rec):
+                big = rec[int(np.argmax(rec[:, 1]))]
+                line += ' largest {}[{},{},{},{}]={}'.format(big[0], big[2], big[3], big[4], big[5], big[1])
+            if int(c.count[0]) > c.comp.shape[1]:
+                line += ' (truncated)'
+            print('components ' + line)
         if args.out:
             from PIL import Image
             from .dataset.cityscape import getpallete

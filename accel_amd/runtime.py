@@ -118,6 +118,9 @@ def _declare(lib):
         "accel_labels_summary": [vp, vp, i, i, i, i, i, i, i, i, vp, sz, vp, vp, vp, vp, sz],
         "accel_model_labels_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
         "accel_model_scores_summary": [vp, i, i, i, i, i, i, i, vp, vp, vp, i, c.POINTER(c.c_int)],
+        "accel_labels_components": [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, vp, vp, sz],
+        "accel_model_labels_components": [vp, i, i, i, i, i, i, i, i, i, i, vp, vp, vp, vp, sz],
+        "accel_model_scores_components": [vp, i, i, i, i, i, i, i, i, i, i, vp, vp, vp, vp, sz],
         "accel_model_labels_forget": [vp],
         "accel_boundary_distance": [vp, vp, i, i, i, sz, i, vp, sz],
         "accel_labels_band_hist": [vp, vp, i, i, i, i, i, vp, i, i, sz, i, c.POINTER(c.c_int), i, vp],
@@ -341,6 +344,24 @@ def _result_rows(out, n, h, w, channels):
     if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable or out.ndim != 3 or out.shape[:2] != (n, h):
         raise ValueError("out must be a writeable C-contiguous uint8 array of n x h x pitch = %d x %d x pitch bytes" % (n, h))
     return out, out.shape[2]
+
+
+def _components_outputs(n, h, w, max_components, comp, sums, ids, width=None):
+    """the destinations of a components call: (count, comp, sums, ids, ids pitch in bytes); comp / sums True or False, ids True, False or the
+    caller's int32 array of n x h x pitch words (only the first w words of every row are written)"""
+    cells = min(max(int(max_components), 0), 65536)
+    count = np.zeros(n, np.int32)
+    c = np.zeros((n, cells, 8), np.int32) if comp else None
+    s = np.zeros((n, cells, 2), np.uint64) if sums else None
+    if ids is None or ids is False:
+        return count, c, s, None, 0
+    if ids is True:
+        return count, c, s, np.empty((n, h, w), np.int32), 4 * w
+    if width is not None and int(width) != w:
+        raise ValueError("width = %d, the rows of ids receive w = %d words" % (int(width), w))
+    if ids.dtype != np.int32 or not ids.flags.c_contiguous or not ids.flags.writeable or ids.ndim != 3 or ids.shape[:2] != (n, h):
+        raise ValueError("ids must be a writeable C-contiguous int32 array of n x h x pitch = %d x %d x pitch words" % (n, h))
+    return count, c, s, ids, 4 * ids.shape[2]
 
 
 def _confidence_outputs(n, h, w, conf, margin, second, hist, labels=None):
@@ -702,6 +723,20 @@ class Context(object):
         opt = lambda v: None if v is None else _fp(v)
         check(lib().accel_labels_summary(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), h, w, ncls, opt(p), pp, opt(s), opt(b), opt(t), opt(k), kp))
         return s, b, t, k
+
+    def labels_components(self, labels, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, comp=True, sums=True, ids=False,
+                          width=None):
+        """accel_labels_components: n x H x W label maps whose valid region is out_h x out_w -> (count, comp, sums, ids) of the connected components
+        of the map at the source size h x w (utils.image.labels_components_host): count n int32, comp n x max_components x 8 int32 = (class, area,
+        x0, y0, x1, y1, ax, ay), sums n x max_components x 2 uint64 = (sum_x, sum_y), ids n x h x w int32.  comp / sums are True or False (left out:
+        None in its place); ids True, False or an int32 array of n x h x pitch words to write the rows into (`width`: the words of a row that are
+        written, w)"""
+        a, n, H, W, _ = _u8_maps(labels)
+        count, c, s, k, kp = _components_outputs(n, int(h), int(w), max_components, comp, sums, ids, width)
+        opt = lambda v: None if v is None else _fp(v)
+        check(lib().accel_labels_components(self.handle, _fp(a), n, H, W, int(out_h), int(out_w), int(h), int(w), int(ncls), int(connectivity),
+                                            int(min_area), int(max_components), _fp(count), opt(c), opt(s), opt(k), kp))
+        return count, c, s, k
 
     def flow_input(self, cur, prev):
         cur, prev = _f32(cur), _f32(prev)
@@ -1200,6 +1235,43 @@ class Model(object):
     def scores_summary_device(self, n, out_h, out_w, h, w, ncls, track=False, stats_ptr=None, box_ptr=None, trans_ptr=None):
         """the same into caller-owned HBM (enqueued, no host wait)"""
         return self._summary_device(lib().accel_model_scores_summary, n, out_h, out_w, h, w, ncls, track, stats_ptr, box_ptr, trans_ptr)
+
+    # ---- connected components of finished frames: they only READ `labels` / `logits` ------------------------------------------------
+    def _components(self, fn, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, comp, sums, ids):
+        n = int(n)
+        count, c, s, k, kp = _components_outputs(n, int(h), int(w), max_components, comp, sums, ids)
+        opt = lambda v: None if v is None else _fp(v)
+        check(fn(self.handle, n, int(out_h), int(out_w), int(h), int(w), int(ncls), int(connectivity), int(min_area), int(max_components), 0,
+                 _fp(count), opt(c), opt(s), opt(k), kp))
+        return count, c, s, k
+
+    def _components_device(self, fn, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, count_ptr, comp_ptr, sums_ptr, ids_ptr,
+                           ids_pitch):
+        vp = lambda v: ctypes.c_void_p(v) if v else None
+        check(fn(self.handle, int(n), int(out_h), int(out_w), int(h), int(w), int(ncls), int(connectivity), int(min_area), int(max_components), 1,
+                 vp(count_ptr), vp(comp_ptr), vp(sums_ptr), vp(ids_ptr), int(ids_pitch if ids_pitch is not None else 4 * int(w))))
+
+    def labels_components(self, n, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, comp=True, sums=True, ids=False):
+        """accel_model_labels_components: (count, comp, sums, ids) of the first n maps of `labels` at the source size h x w, as numpy arrays (see
+        Context.labels_components).  It only READS `labels`"""
+        return self._components(lib().accel_model_labels_components, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, comp, sums, ids)
+
+    def labels_components_device(self, n, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, count_ptr=None, comp_ptr=None,
+                                 sums_ptr=None, ids_ptr=None, ids_pitch=None):
+        """the same into caller-owned HBM (enqueued, no host wait): n int32, n x max_components x 8 int32, n x max_components x 2 uint64 and
+        n x h rows of w int32 `ids_pitch` bytes apart (default 4 * w)"""
+        self._components_device(lib().accel_model_labels_components, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, count_ptr,
+                                comp_ptr, sums_ptr, ids_ptr, ids_pitch)
+
+    def scores_components(self, n, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, comp=True, sums=True, ids=False):
+        """accel_model_scores_components: labels_components with the labels of the interpolated scores; ncls is the class count of `logits`"""
+        return self._components(lib().accel_model_scores_components, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, comp, sums, ids)
+
+    def scores_components_device(self, n, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, count_ptr=None, comp_ptr=None,
+                                 sums_ptr=None, ids_ptr=None, ids_pitch=None):
+        """the same into caller-owned HBM (enqueued, no host wait)"""
+        self._components_device(lib().accel_model_scores_components, n, out_h, out_w, h, w, ncls, connectivity, min_area, max_components, count_ptr,
+                                comp_ptr, sums_ptr, ids_ptr, ids_pitch)
 
     def labels_forget(self):
         """accel_model_labels_forget: drop the kept map (a new clip, a cut): the next tracked summary compares with nothing"""

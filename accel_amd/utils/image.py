@@ -926,6 +926,131 @@ def summary_churn(trans):
         return np.where(total > 0, 1.0 - trace / total, np.nan)
 
 
+# ---- connected components of finished frames: objects per class (csrc/labels_components.hip restates it bit for bit) ---------------------------
+def labels_components_host(labels, out_h, out_w, h, w, ncls, connectivity=8, min_area=1, max_components=1024, ids=False):
+    """The specification of accel_labels_components.  `labels` is [n x] H x W uint8 with the valid region out_h x out_w; L is the map at the source
+    size h x w under the nearest rule (labels_to_source_host).  A pixel with L >= ncls is background: it belongs to no component and separates
+    components.  Two other pixels of one frame are joined when their labels are equal and they are 4-adjacent (connectivity=8: or diagonally
+    adjacent); a component is a class of the transitive closure, its anchor its first pixel in raster order (the smallest y * w + x).  The
+    REPORTED components of a frame are those with area >= min_area, in ascending anchor order.  Returns (count, comp, sums[, ids]):
+        count  n int32: the reported components of the frame -- the full number, also above max_components
+        comp   n x max_components x 8 int32: (class, area, x0, y0, x1, y1, ax, ay) of the first min(count, max_components) of them -- the
+               inclusive box and the anchor -- and -1 in the records after them
+        sums   n x max_components x 2 uint64: (sum_x, sum_y) over the component's source pixels; 0 in the unused records
+        ids    n x h x w int32 (ids=True): per source pixel the index of its component's record; -1 for background, for components below
+               min_area and for components beyond max_components
+    Pure integer arithmetic: rows are cut into runs, runs of adjacent rows are united towards the smaller run (a union-find over runs)."""
+    a = np.asarray(labels, np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("labels must be [n x] H x W uint8, got shape %s" % (a.shape,))
+    n, H, W = a.shape
+    out_h, out_w, h, w, ncls = int(out_h), int(out_w), int(h), int(w), int(ncls)
+    connectivity, min_area, max_components = int(connectivity), int(min_area), int(max_components)
+    if not (1 <= out_h <= H and 1 <= out_w <= W):
+        raise ValueError("out_h x out_w = %d x %d, must be in 1 x 1 .. H x W = %d x %d" % (out_h, out_w, H, W))
+    if not (1 <= h <= 32768 and 1 <= w <= 32768):
+        raise ValueError("h x w = %d x %d, must be in 1 .. 32768" % (h, w))
+    if not 1 <= ncls <= 32:
+        raise ValueError("ncls = %d, must be in 1 .. 32" % ncls)
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity = %d, must be 4 or 8" % connectivity)
+    if min_area < 1:
+        raise ValueError("min_area = %d, must be >= 1" % min_area)
+    if not 1 <= max_components <= 65536:
+        raise ValueError("max_components = %d, must be in 1 .. 65536" % max_components)
+    src = labels_to_source_host(a, out_h, out_w, h, w)
+    reach = 1 if connectivity == 8 else 0
+    count = np.zeros(n, np.int32)
+    comp = np.full((n, max_components, 8), -1, np.int32)
+    sums = np.zeros((n, max_components, 2), np.uint64)
+    pix = np.full((n, h, w), -1, np.int32) if ids else None
+    for f in range(n):
+        L = src[f]
+        start = L < ncls
+        start[:, 1:] &= L[:, 1:] != L[:, :-1]
+        ry, rx0 = np.nonzero(start)                              # the runs, in raster order of their first pixels
+        nr = ry.size
+        if not nr:
+            continue
+        stop = L < ncls
+        stop[:, :-1] &= L[:, :-1] != L[:, 1:]
+        rx1 = np.nonzero(stop)[1]
+        rl = L[ry, rx0]
+        first = np.searchsorted(ry, np.arange(h + 1))            # the first run of every row
+        parent = list(range(nr))
+        y_, x0_, x1_, l_, first_ = ry.tolist(), rx0.tolist(), rx1.tolist(), rl.tolist(), first.tolist()
+
+        def join(i, j):
+            if x0_[i] <= x1_[j] + reach and x0_[j] <= x1_[i] + reach and l_[i] == l_[j]:
+                while parent[i] != i:
+                    i = parent[i]
+                while parent[j] != j:
+                    j = parent[j]
+                if i < j:
+                    parent[j] = i
+                elif j < i:
+                    parent[i] = j
+
+        for y in range(1, h):
+            i, i_end, j, j_end = first_[y - 1], first_[y], first_[y], first_[y + 1]
+            while i < i_end and j < j_end:                       # the run that ends first has met every run of the other row it can touch
+                join(i, j)
+                if x1_[i] < x1_[j]:
+                    i += 1
+                elif x1_[j] < x1_[i]:
+                    j += 1
+                else:                                            # both end here: the next run of either row may still touch the other diagonally
+                    if i + 1 < i_end:
+                        join(i + 1, j)
+                    j += 1
+        for i in range(nr):                                      # parent[i] <= i: one pass in raster order makes every run point at its root
+            parent[i] = parent[parent[i]]
+        root = np.asarray(parent, np.int64)
+        x0, x1, yy = rx0.astype(np.int64), rx1.astype(np.int64), ry.astype(np.int64)
+        length = x1 - x0 + 1
+        area, sx, sy = np.zeros(nr, np.int64), np.zeros(nr, np.int64), np.zeros(nr, np.int64)
+        np.add.at(area, root, length)
+        np.add.at(sx, root, (x0 + x1) * length // 2)
+        np.add.at(sy, root, yy * length)
+        bx0, by0, bx1, by1 = np.full(nr, w, np.int64), np.full(nr, h, np.int64), np.full(nr, -1, np.int64), np.full(nr, -1, np.int64)
+        np.minimum.at(bx0, root, x0)
+        np.minimum.at(by0, root, yy)
+        np.maximum.at(bx1, root, x1)
+        np.maximum.at(by1, root, yy)
+        keep = np.nonzero((root == np.arange(nr)) & (area >= min_area))[0]      # ascending run index: ascending anchor
+        count[f] = keep.size
+        keep = keep[:max_components]
+        k = keep.size
+        comp[f, :k] = np.stack([rl[keep].astype(np.int64), area[keep], bx0[keep], by0[keep], bx1[keep], by1[keep], x0[keep], yy[keep]], axis=1)
+        sums[f, :k, 0] = sx[keep].astype(np.uint64)
+        sums[f, :k, 1] = sy[keep].astype(np.uint64)
+        if ids:
+            slot = np.full(nr, -1, np.int32)
+            slot[keep] = np.arange(k, dtype=np.int32)
+            per_run = slot[root]
+            flat = pix[f].reshape(-1)
+            at = np.repeat(yy * w + x0 - np.cumsum(length) + length, length) + np.arange(int(length.sum()))
+            flat[at] = np.repeat(per_run, length)
+    return (count, comp, sums, pix) if ids else (count, comp, sums)
+
+
+def components_centroids(comp, sums):
+    """(sum_x / area, sum_y / area) of labels_components_host's records: float64 [...] x max_components x 2, NaN in the unused records"""
+    area = np.asarray(comp)[..., 1:2].astype(np.float64)
+    s = np.asarray(sums).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(area > 0, s / area, np.nan)
+
+
+def components_of(result, frame):
+    """the trimmed records of one frame of a (count, comp, sums[, ids]) result: (comp k x 8, sums k x 2) with k = min(count, max_components)"""
+    count, comp, sums = result[0], result[1], result[2]
+    k = min(int(count[frame]), comp.shape[1])
+    return comp[frame, :k], sums[frame, :k]
+
+
 # ---- trimap evaluation: the confusion matrix in bands around the ground truth's boundaries (csrc/labels_band.hip restates it bit for bit) --------
 def _u8_batch(maps, what):
     a = np.asarray(maps, np.uint8)

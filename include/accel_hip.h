@@ -553,6 +553,46 @@ int accel_model_scores_summary(accel_model* m, int n, int out_h, int out_w, int 
                                uint64_t* stats, int32_t* box, uint64_t* trans, int dst_on_device, int* compared);
 int accel_model_labels_forget(accel_model* m);
 
+/* ---- finished frames: connected components, the objects of every class ---------------------------------------------------
+ * The summary above says "class car covers 3 % of the frame, inside this box"; this says "four cars, here, here, here and
+ * here" (csrc/labels_components.hip).  The geometry vocabulary and L(f, y, x) are those of the summary.  A source pixel with
+ * L >= ncls (ncls in 1 .. 32) is background: it belongs to no component and separates components.  Two other pixels of one
+ * frame are joined when their labels are equal and they are 4-adjacent -- with connectivity = 8 also when they are diagonally
+ * adjacent; a component is a class of the transitive closure and its ANCHOR is its first pixel in raster order (the smallest
+ * y * w + x).  Frames never join.  The REPORTED components of a frame are those with area >= min_area (>= 1), in ascending
+ * anchor order:
+ *   count    n int32                        the reported components of the frame: the full number, also above max_components
+ *   comp     n x max_components x 8 int32   (class, area, x0, y0, x1, y1, ax, ay) of the first min(count, max_components) of
+ *                                           them: the inclusive box and the anchor; -1 in the records after them
+ *   sums     n x max_components x 2 uint64  (sum_x, sum_y) over the component's source pixels (the centroid is sum / area); 0
+ *                                           in the unused records
+ *   ids      n x h rows of w int32, `ids_pitch` bytes apart (>= 4 * w, a multiple of 4): per source pixel the index of its
+ *            component's record; -1 for background, for components below min_area and for components beyond
+ *            max_components.  Only the w words of a row are written
+ * count is required; comp, sums and ids may each be NULL.  max_components is in 1 .. 65536.  All of it is integer and exact:
+ * the specification is accel_amd/utils/image.py labels_components_host and the kernels equal it bit for bit.  Nothing outside
+ * out_h x out_w of `labels` is read.  Argument errors (a NULL handle, labels or count, a size < 1 or > 32768, out_h > H,
+ * out_w > W, ncls outside 1 .. 32, connectivity other than 4 or 8, min_area < 1, max_components outside 1 .. 65536, an
+ * ids_pitch below 4 * w or not a multiple of 4, a misaligned device destination, n larger than the bound batch, no `labels` /
+ * `logits` buffer, scores of another class count than ncls) return ACCEL_ERR_ARG before anything is enqueued.
+ *   accel_labels_components         operator level: host bytes in, host results out (the parity tests)
+ *   accel_model_labels_components   on the model's `labels` buffer, enqueued on the context stream after the run that wrote it.
+ *                                   It only reads `labels`.  The scratch (two int32 per source pixel and one per 1024 of them)
+ *                                   is model-owned, allocated on first use, kept for the next frame and freed with the model.
+ *                                   Host destinations (dst_on_device = 0) go through the staging buffer and the call waits;
+ *                                   device destinations (4-byte aligned, sums 8-byte) are enqueued only
+ *   accel_model_scores_components   the same with the labels of the bilinearly interpolated scores (accel_model_scores_labels):
+ *                                   ncls must be the class count of `logits`.  It only reads `logits` */
+int accel_labels_components(accel_ctx* ctx, const uint8_t* labels, int n, int H, int W, int out_h, int out_w, int h, int w, int ncls,
+                            int connectivity, int min_area, int max_components,
+                            int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids, size_t ids_pitch);
+int accel_model_labels_components(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int connectivity, int min_area,
+                                  int max_components, int dst_on_device, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                                  size_t ids_pitch);
+int accel_model_scores_components(accel_model* m, int n, int out_h, int out_w, int h, int w, int ncls, int connectivity, int min_area,
+                                  int max_components, int dst_on_device, int32_t* count, int32_t* comp, uint64_t* sums, int32_t* ids,
+                                  size_t ids_pitch);
+
 /* ---- finished frames: trimap evaluation, the confusion matrix in bands around the ground truth's boundaries ------------
  * Whole-frame mIoU is dominated by interior pixels; what feature propagation costs sits at object boundaries.  For a
  * ground-truth map g (h x w uint8, rows `gt_pitch` apart; the frames of a batch are independent):
